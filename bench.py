@@ -1,13 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the wgebra dense hot path on MI355X, against its roofline, with the CPU port beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one batch of synthetic input that is already resident in HBM:
 one Gemm / Gemv / batched Reduce dispatch (for N > 1: the M-sharded Gemm of every rank + the RCCL all-gather of C).
 Rank 0 prints ONE JSON line (schema: see DESIGN.md "Measurement").
+
+A plain run sets up, warms up, times exactly --steps steps of the one workload and prints the line. --full adds everything else the
+line can carry: the sanity check of the result against f64, the CPU port baseline, the MFMA-only ceiling, every secondary workload,
+the per-panel exchange waits of a multi-rank run and the --detail sidecar by default. --dump-outputs DIR writes what the timed path
+computed in its last step (the workload's output tensors, as float32; a seeded sample of a large one) to DIR/<name>.npy.
 
 Workloads (BASELINE.json `configs`):
   gemm_f32_4096         f32 GEMM 4096^3           (configs[1])   MFMA-bound   TFLOP/s
@@ -235,6 +240,44 @@ def device_random(wg, gpu, shape, dtype, seed):
     return t
 
 
+# --dump-outputs: every array of a run together stays under DUMP_MAX_BYTES; an output larger than DUMP_SAMPLE_BYTES (as float32) is written as a
+# seeded sample of whole lines (the columns of a column-major matrix, the rows of a row-major one) -- the same lines in every run of the same arguments
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SAMPLE_BYTES = 32 << 20
+
+
+def read_elems(gpu, t, start, n, dtype) -> np.ndarray:
+    """Elements [start, start + n) of the buffer of tensor `t`, read to the host."""
+    from wgmath_amd._lib import check, lib
+    item = np.dtype(dtype).itemsize
+    out = np.empty(n, dtype)
+    check(lib.wg_buf_read(gpu._ctx.handle, t._h, start * item, out.ctypes.data, n * item))
+    return out
+
+
+def read_lines(gpu, t, nlines, line_len, dtype, seed):
+    """The buffer of `t` as `nlines` contiguous lines of `line_len` elements, in float32: (all of them, False) when they fit DUMP_SAMPLE_BYTES, else
+    (a seeded choice of whole lines in ascending order, True). Shape (lines, line_len)."""
+    if nlines * line_len * 4 <= DUMP_SAMPLE_BYTES:
+        return read_elems(gpu, t, 0, nlines * line_len, dtype).astype(np.float32).reshape(nlines, line_len), False
+    k = max(1, min(nlines, DUMP_SAMPLE_BYTES // (line_len * 4)))
+    idx = np.sort(np.random.default_rng(seed).choice(nlines, k, replace=False))
+    return np.stack([read_elems(gpu, t, int(i) * line_len, line_len, dtype) for i in idx]).astype(np.float32), True
+
+
+def dump_outputs(w, path) -> list:
+    """Writes the workload's outputs as they stand (after its last step) to path/<name>.npy. Returns the names written."""
+    outs = w.outputs()
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"{w.name}: {total} bytes of outputs (> {DUMP_MAX_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for name, a in outs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(outs)
+
+
 # ------------------------------------------------------------------------------------------------------------
 # workloads
 # ------------------------------------------------------------------------------------------------------------
@@ -275,6 +318,7 @@ class Workload:
     def algorithmic_per_launch(self) -> float: ...  # this rank's dominant kernel, per launch
     def cpu_baseline(self, budget_s: float) -> dict: ...
     def check(self) -> None: ...                  # cheap sanity check of the result (not timed)
+    def outputs(self) -> dict: ...                # what a caller of the step receives, float32 on the host (--dump-outputs)
 
     def algorithmic_bytes(self) -> float:
         """Compulsory HBM bytes of one launch of the dominant kernel (operands read once, result written once): what the measured
@@ -431,6 +475,11 @@ class GemmWorkload(Workload):
             ulp = np.spacing(scale.astype(self.np_dtype)).astype(np.float64)
             self.max_ulp_vs_f64 = max(getattr(self, "max_ulp_vs_f64", 0.0), float((err / ulp).max()))
 
+    def outputs(self):
+        """C (M x N, column-major; every rank holds all of it): the whole matrix, or a seeded sample of its columns (M x k)."""
+        cols, sampled = read_lines(self.gpu, self.C, self.N, self.M, self.np_dtype, seed=0xC0)
+        return {"C_columns_sample" if sampled else "C": np.ascontiguousarray(cols.T)}
+
     def cpu_baseline(self, budget_s):
         # The reference's only GEMM is the f32 WGSL kernel; its CPU port is timed on a slice with the SAME K
         # (for the f16 workloads this is still the f32 port: there is no reference f16 path to port).
@@ -508,6 +557,11 @@ class RowMajorGemmWorkload(GemmWorkload):
         assert (err <= tol).all(), f"bench sanity check failed (row-major): worst err/tol {(err / tol).max():.3g}"
         scale = sabs if self.dtype == "f32" else np.abs(truth)
         self.max_ulp_vs_f64 = float((err / np.spacing(scale.astype(self.np_dtype)).astype(np.float64)).max())
+
+    def outputs(self):
+        """C (M x N, row-major): the whole matrix, or a seeded sample of its rows (k x N)."""
+        rows, sampled = read_lines(self.gpu, self.C, self.M, self.N, self.np_dtype, seed=0xC0)
+        return {"C_rows_sample" if sampled else "C": rows}
 
 
 class FewColumnsGemmWorkload(GemmWorkload):
@@ -614,6 +668,11 @@ class GemvWorkload(Workload):
         ulp = np.spacing(scale.astype(self.np_dtype)).astype(np.float64)
         self.max_ulp_vs_f64 = float((np.abs(got[idx] - truth) / ulp).max())
 
+    def outputs(self):
+        olen = self.C if self.trans else self.R
+        out = self.out.read(self.gpu.device()).astype(np.float32).reshape(olen, self.nrhs, order="F")
+        return {"out": out[:, 0].copy() if self.nrhs == 1 else np.ascontiguousarray(out)}
+
     def cpu_baseline(self, budget_s):
         from oracle import wgsl_oracle as wo
         C = wo.CLib()
@@ -677,6 +736,9 @@ class ReduceWorkload(Workload):
             col = x[c * self.n:(c + 1) * self.n].astype(np.float64)
             assert abs(float(got[c]) - col.sum()) <= self.n * 2.0 ** -24 * np.abs(col).sum(), "bench sanity check failed (reduce)"
 
+    def outputs(self):
+        return {"res": self.res.read(self.gpu.device()).astype(np.float32)}
+
     def cpu_baseline(self, budget_s):
         from oracle import wgsl_oracle as wo
         C = wo.CLib()
@@ -728,6 +790,12 @@ class OpAssignWorkload(Workload):
             exp = exp + self.b0
         got = self.a.read(self.gpu.device())[:4096]
         assert got.tobytes() == exp.tobytes(), "bench sanity check failed (op_assign is not bit-exact)"
+
+    def outputs(self):
+        """a after the last step: the whole vector, or a seeded sample of its 65536-element pieces (k x 65536)."""
+        piece = 65536 if self.n % 65536 == 0 else self.n
+        a, sampled = read_lines(self.gpu, self.a, self.n // piece, piece, np.float32, seed=0xA0)
+        return {"a_pieces_sample": a} if sampled else {"a": a.reshape(-1)}
 
     def cpu_baseline(self, budget_s):
         from oracle import wgsl_oracle as wo
@@ -837,10 +905,11 @@ def load_pmc(workload: str):
     return out
 
 
-def run_workload(wg, gpu, name, steps, warmup, rank, world, barrier, with_cpu, cpu_budget, min_seconds=0.0, keep=True, agree=None):
+def run_workload(wg, gpu, name, steps, warmup, rank, world, barrier, with_cpu, cpu_budget, min_seconds=0.0, keep=True, agree=None, check=True, dump=None):
     """Times EXACTLY `steps` steps (after `warmup` untimed ones). With min_seconds > 0 (secondary configs only) `steps` is raised
     so that the timed region lasts at least that long: millisecond kernels timed for a few tens of ms still see the clocks
-    ramping (measured: f32 GEMM 140 TF over 30 ms vs 148 TF sustained)."""
+    ramping (measured: f32 GEMM 140 TF over 30 ms vs 148 TF sustained). `dump`: a directory that receives the outputs of the last
+    step (dump_outputs); `check`: the sanity check of the result against f64 (untimed)."""
     w = WORKLOADS[name]()
     setup_err = None
     try:
@@ -886,7 +955,9 @@ def run_workload(wg, gpu, name, steps, warmup, rank, world, barrier, with_cpu, c
     ev = ts.wait_for_results_ms()
     launches = getattr(w, "launches_per_step", lambda: 1)()
     kernel_ms = (ev[1] - ev[0]) / (steps * launches)  # HIP events on the stream the kernels run on
-    if not os.environ.get("WG_BENCH_NO_CHECK"):
+    if dump:
+        log(f"[bench] {name}: outputs of the last step written to {dump}: {', '.join(dump_outputs(w, dump))}")
+    if check and not os.environ.get("WG_BENCH_NO_CHECK"):
         w.check()
     if agree is not None:
         barrier()  # every rank is past its checks: nobody reads a peer's buffers any more
@@ -1220,10 +1291,19 @@ def main():
                     help="exchange engine of the M-sharded Gemm with N > 1 ranks: RCCL all-gather (+ relayout) with 8 or 4 CUs left to its kernels, "
                          "staged contiguous peer copies (+ relayout), or auto = a short trial of each as a fresh child group, the timed steps on the fastest")
     ap.add_argument("--dry-run", action="store_true", help="multi-rank plumbing test without a GPU (gloo, host arithmetic)")
-    ap.add_argument("--detail", default=os.environ.get("WG_BENCH_DETAIL", DEFAULT_DETAIL),
+    ap.add_argument("--detail", default=None,
                     help="sidecar file for the full record (the stdout line + `others`: every secondary workload's roofline / cpu_baseline objects, and "
-                         "`ranks_detail`); '-' = none. The same text goes to stderr as `[bench detail] {...}`")
+                         "`ranks_detail`); '-' = none (the default of a run without --full). The same text goes to stderr as `[bench detail] {...}`")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the sanity check against f64, the CPU port baseline, the MFMA-only ceiling, the secondary "
+                         "workloads, the per-panel exchange waits of a multi-rank run, and the detail sidecar by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32; a seeded sample of a large output)")
     args = ap.parse_args()
+    if args.detail is None:
+        args.detail = os.environ.get("WG_BENCH_DETAIL", DEFAULT_DETAIL if args.full else "-")
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     VALUES = args.dist
     os.environ["WG_BENCH_VALUES"] = args.dist  # (self-launched ranks inherit it)
 
@@ -1361,7 +1441,7 @@ def main():
         import torch
         import torch.distributed as dist
         try:
-            r = run_workload(wg, gpu, args.workload, max(2, args.warmup), 1, rank, world, barrier, False, 0.0, keep=False, agree=agree)
+            r = run_workload(wg, gpu, args.workload, max(2, args.warmup), 1, rank, world, barrier, False, 0.0, keep=False, agree=agree, check=args.full)
             el, err = r["elapsed"] / r["steps"], None
         except Exception as e:
             el, err = float("inf"), f"{type(e).__name__}: {e}"
@@ -1385,7 +1465,7 @@ def main():
             DIST.update(comm=cm, mode=mode)
             gpu = g
             try:
-                r = run_workload(wg, g, args.workload, max(2, args.warmup), 1, rank, world, barrier, False, 0.0, keep=False, agree=agree)
+                r = run_workload(wg, g, args.workload, max(2, args.warmup), 1, rank, world, barrier, False, 0.0, keep=False, agree=agree, check=args.full)
                 el = r["elapsed"] / r["steps"]
                 err = None
             except Exception as e:
@@ -1403,7 +1483,8 @@ def main():
         info = gpu.adapter()
 
     main_res = run_workload(wg, gpu, args.workload, args.steps, args.warmup, rank, world, barrier,
-                            not args.no_cpu_baseline, args.cpu_budget, agree=agree if dist_mode else None)
+                            args.full and not args.no_cpu_baseline, args.cpu_budget, agree=agree if dist_mode else None, check=args.full,
+                            dump=args.dump_outputs if rank == 0 else None)
     elapsed = main_res["elapsed"]
     rank_detail, rank_flat = None, {}
     if dist_mode:
@@ -1415,7 +1496,7 @@ def main():
         elapsed = float(t.item())
         # a few steps more, outside the timed region, with the compute stream stamped around every wait for a panel's exchange
         waits, wl = [], main_res["workload"]
-        if isinstance(wl, GemmWorkload) and wl.dist is not None:
+        if args.full and isinstance(wl, GemmWorkload) and wl.dist is not None:
             cm = wl.dist["comm"]
             barrier()
             ok = True
@@ -1448,7 +1529,7 @@ def main():
             rank_detail, rank_flat = ranks_detail(per_rank, getattr(wl, "npanels", 1))
     w = main_res["workload"]
     global MFMA_CEILING
-    if world == 1 and not dist_mode and w.dtype == "f16" and w.bound == "mfma" and os.environ.get("WG_BENCH_NO_CEILING") != "1":
+    if args.full and world == 1 and not dist_mode and w.dtype == "f16" and w.bound == "mfma" and os.environ.get("WG_BENCH_NO_CEILING") != "1":
         try:  # right behind the headline's steps, on the same warm chip
             MFMA_CEILING = gpu.mfma_ceiling(0.6)
         except Exception as e:  # noqa: BLE001 -- a diagnostic must not take the line down
@@ -1481,7 +1562,7 @@ def main():
         barrier()
     w = None
     others = []
-    if world == 1 and not dist_mode and not args.no_secondary:
+    if args.full and world == 1 and not dist_mode and not args.no_secondary:
         for name in SECONDARY:
             if name == args.workload or name in args.skip.split(","):
                 continue
@@ -1495,7 +1576,7 @@ def main():
             except Exception as e:  # a secondary config must never take the headline down with it
                 others.append({"workload": name, "error": f"{type(e).__name__}: {e}"})
 
-    if dist_mode and not args.no_secondary and not oversub:
+    if args.full and dist_mode and not args.no_secondary and not oversub:
         import torch
         import torch.distributed as dist
         saved, DIST = DIST, None  # the HBM-bound operators shard by independent units: no communicator

@@ -197,3 +197,48 @@ def test_panel_planner_properties():
                         return (-(-t // cus)) * cus / t
                     best = min(round(waste(c), 3) for c in range(1, n // tile + 1) if -(-(n // tile) // c) >= 2 or n // tile < 2)
                     assert round(waste(pc // tile), 3) <= best + 1e-9, (mg, n, cus, tile, pc)
+
+
+def test_read_lines_takes_all_or_the_same_seeded_whole_lines(monkeypatch):
+    """bench.read_lines (--dump-outputs) on a host array standing in for a device buffer: all of it while it fits the sample size, else the
+    same seeded choice of whole lines in every call, in ascending order."""
+    import numpy as np
+
+    import bench
+    buf = np.arange(64 * 100, dtype=np.float16)
+    monkeypatch.setattr(bench, "read_elems", lambda gpu, t, start, n, dtype: buf[start:start + n].astype(dtype))
+    whole, sampled = bench.read_lines(None, None, 64, 100, np.float16, seed=1)
+    assert not sampled and whole.dtype == np.float32 and whole.shape == (64, 100) and (whole.reshape(-1) == buf.astype(np.float32)).all()
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 10 * 100 * 4)
+    a, sampled = bench.read_lines(None, None, 64, 100, np.float16, seed=1)
+    b, _ = bench.read_lines(None, None, 64, 100, np.float16, seed=1)
+    assert sampled and a.shape == (10, 100) and np.array_equal(a, b)
+    first = a[:, 0].astype(np.int64)
+    assert (first % 100 == 0).all() and (np.diff(first) > 0).all()  # whole lines, ascending
+    assert all(np.array_equal(a[i], buf[f:f + 100].astype(np.float32)) for i, f in enumerate(first))
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    import numpy as np
+    import pytest
+
+    import bench
+
+    class W:
+        name = "w"
+
+        def __init__(self, outs):
+            self.outs = outs
+
+        def outputs(self):
+            return self.outs
+    assert bench.dump_outputs(W({"C": np.ones((4, 3), np.float32), "res": np.zeros(5)}), str(tmp_path / "d")) == ["C", "res"]
+    assert np.load(tmp_path / "d" / "C.npy").shape == (4, 3) and np.load(tmp_path / "d" / "res.npy").dtype == np.float64
+    with pytest.raises(ValueError):
+        bench.dump_outputs(W({"big": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)}), str(tmp_path / "e"))
+    assert not (tmp_path / "e").exists()
+
+
+def test_plain_and_full_runs_are_options():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout

@@ -338,7 +338,7 @@ def test_two_processes_one_gpu_config5_full_size_staged():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, WG_BENCH_OVERSUBSCRIBE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", WG_BENCH_LAUNCH_TIMEOUT="600")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--gather", "staged", "--steps", "2", "--warmup", "1",
-                        "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
+                        "--full", "--no-secondary", "--no-cpu-baseline"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["workload"] == "gemm_f16_32768" and line["config"]["gather_engine"] == "staged"
@@ -392,7 +392,7 @@ def _bench_line(*argv, env=None):
 
 
 def test_bench_line_ends_with_targets_and_carries_the_measured_clock():
-    line = _bench_line("--workload", "gemm_f16_8192", "--steps", "20", "--warmup", "5", "--no-secondary", "--no-cpu-baseline")
+    line = _bench_line("--workload", "gemm_f16_8192", "--steps", "20", "--warmup", "5", "--full", "--no-secondary", "--no-cpu-baseline")
     assert list(line)[-1] == "targets" and all(not isinstance(v, (dict, list)) for v in line["targets"].values())
     rf, t = line["roofline"], line["targets"]
     assert 0.8 < rf["clock_ghz_measured"] < 2.6 and rf["clock_ghz_xcd_min_max"][0] <= rf["clock_ghz_measured"] <= rf["clock_ghz_xcd_min_max"][1]
@@ -415,7 +415,7 @@ def test_default_bench_line_fits_the_driver_and_the_sidecar_holds_the_rest(tmp_p
     e.pop("WORLD_SIZE", None)
     e.pop("RANK", None)
     side = tmp_path / "detail.json"
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--secondary-seconds", "0.05", "--cpu-budget", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--secondary-seconds", "0.05", "--cpu-budget", "2",
                         "--detail", str(side)], capture_output=True, text=True, env=e, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -439,10 +439,32 @@ def test_default_bench_line_fits_the_driver_and_the_sidecar_holds_the_rest(tmp_p
 
 
 def test_bench_communicator_path_reports_rccl_rank_count_and_cu_split():
-    line = _bench_line("--workload", "gemm_f16_8192", "--gather", "rccl", "--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline",
+    line = _bench_line("--workload", "gemm_f16_8192", "--gather", "rccl", "--steps", "3", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline",
                        env={"WG_BENCH_FORCE_DIST": "1"})
     cfg = line["config"]
     assert cfg["gather_engine"] == "rccl" and cfg["ranks"] == 1
     assert cfg["rccl_reported_ranks"] == 1  # ncclCommCount through wg_comm_reported_size
     assert cfg["comm_compute_units"] == 0 and cfg["stream_compute_units"] == cfg["compute_units"]  # one rank: nothing to leave to RCCL
     assert list(line)[-1] == "targets"
+
+
+def test_plain_bench_run_is_the_headline_alone_and_dumps_what_the_last_step_computed(tmp_path):
+    """Without --full the run times its one workload and prints the line (no check, CPU baseline, ceiling, secondary workloads or sidecar);
+    --dump-outputs writes what the last step computed: here all of C of an f16 2048^3 Gemm, which must be the product of the operands the bench
+    generated (device_random: one seeded block, here the whole operand) within the f16 Gemm's bound."""
+    import bench
+    out = tmp_path / "outputs"
+    line = _bench_line("--workload", "gemm_f16_2048", "--steps", "4", "--warmup", "1", "--dump-outputs", str(out), env={"WG_BENCH_VALUES": "pm1"})
+    assert line["metric"] == "gemm_tflops" and line["unit"] == "TFLOP/s" and line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert line["steps"] == 4 and line["ms_per_step"] > 0 and line["value"] > 0 and list(line)[-1] == "targets"
+    assert line["cpu_baseline"] is None and line["detail"] is None and "mfma_only_ceiling_tflops" not in line["roofline"]
+    assert sorted(os.listdir(out)) == ["C.npy"]
+    C = np.load(out / "C.npy")
+    assert C.dtype == np.float32 and C.shape == (2048, 2048)
+    n = 2048
+    A = bench.rand_block(0xA000, n * n, np.float16).astype(np.float64).reshape(n, n, order="F")
+    B = bench.rand_block(0xB000, n * n, np.float16).astype(np.float64).reshape(n, n, order="F")
+    truth, sabs = A @ B, np.abs(A) @ np.abs(B)
+    tol = 2 * np.sqrt(n) * 2.0 ** -24 * sabs + 2.0 ** -11 * np.abs(truth) + 2.0 ** -25
+    err = np.abs(C.astype(np.float64) - truth)
+    assert (err <= tol).all(), f"dumped C: worst err/tol {(err / tol).max():.3g}"

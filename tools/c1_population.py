@@ -17,7 +17,7 @@ cands = sys.argv[1:] or ["gemv_f32_1024", "op_assign_f32_256M", "reduce_f32_4096
 skip = ",".join(n for n in bench.SECONDARY if n != GRAPH)
 for x in cands:
     side = f"/tmp/c1pop_{x}.json"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", x, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--skip", skip, "--detail", side],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", x, "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--skip", skip, "--detail", side],
                        capture_output=True, text=True, env=dict(os.environ, WG_BENCH_NO_CHECK="1", WG_BENCH_NO_CEILING="1"), timeout=600)
     try:
         d = json.load(open(side))

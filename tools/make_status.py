@@ -3,7 +3,7 @@
 
     python tools/make_status.py profiles/r06_bench*_detail.json [--vendor profiles/r06_vendor_vs_ours.txt] > STATUS.md
 
-Every figure comes out of a file named in the page itself: a bench line is the JSON `python bench.py` printed on one box (one file = one box's
+Every figure comes out of a file named in the page itself: a bench line is the JSON `python bench.py --full` printed on one box (one file = one box's
 run), the vendor column out of tools/vendor_vs_ours.sh's text (lines `<workload> ... ours <x> TF ... vendor <y> TF`). Re-run after every bench run."""
 import json
 import os
