@@ -35,7 +35,9 @@
 extern "C" {
 #endif
 
-#define WGEBRA_HIP_ABI_VERSION 4 /* 4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
+#define WGEBRA_HIP_ABI_VERSION 5 /* 5: wg_debug_take_path; and the round-6 additions that came without a bump: wg_copy_view, wg_timestamps_reserve,
+                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE;
+                                    4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -170,6 +172,11 @@ int wg_debug_spin(wg_ctx *ctx, uint32_t blocks, uint32_t usec, wg_buf *start_tic
 int wg_debug_clock_begin(wg_ctx *ctx);
 int wg_debug_clock_end(wg_ctx *ctx, double *ghz_mean, double *ghz_min, double *ghz_max, double *seconds);
 int wg_debug_mfma_ceiling(wg_ctx *ctx, double min_seconds, double *tflops, double *clock_ghz);
+/* Which leaves of the Gemm / Gemv launchers' dispatch trees ran since the last call (tests): one short tag per terminal launch, space-separated --
+ * "f32.big/ns=4 splitk.reduce/ns=4", "f16.cont", "f16.pad/c=seed>f16.t128/ns=1" (a tag ending in '>' wraps the next one: staging, padding, transposed
+ * forms). Equal logs mean the same kernels in the same summation order. Host-side bookkeeping only; the context keeps the newest few hundred bytes.
+ * Copies the log into buf (NUL-terminated, truncated to cap - 1 bytes) and clears it; buf may be NULL to just clear it. */
+int wg_debug_take_path(wg_ctx *ctx, char *buf, size_t cap);
 
 /*
  * Kernel-selection knobs of a context (tests and experiments; production code never needs them). The launchers choose between
@@ -279,7 +286,8 @@ int wg_gemm_ex(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, float alpha
  * column y < out.size[1] and matrix z < out.size[2]; `out` is overwritten.
  *   DIM_MISMATCH  : gemv.rs:89-90 (only m_cols == v_rows and m_rows == out_rows are checked there too).
  *   PRECONDITION  : WG_GEMV_FAST / WG_GEMV_TR_FAST with out rows % 4 != 0 (assert_eq! gemv.rs:122). Views that are not
- *                   vec4-aligned run in ONE pass on the matrix where it lies (gemv_any.hip: 16-byte loads at element-aligned addresses).
+ *                   vec4-aligned run on the matrix where it lies, one pass over it per right-hand side (gemv_any.hip: 16-byte loads at
+ *                   element-aligned addresses).
  *   WG_GEMV_TR_FAST with m rows % 128 != 0 silently runs as WG_GEMV_TR (gemv.rs:99-104) -- same kernel here.
  * dtype WG_F16 (extension): f16 elements, f32 accumulation, one rounding at the store -- the same HBM-bound kernels.
  * Several right-hand sides: one pass over the matrix for all of them; from 9 on -- and from 3 on when the matrix is past the launch-bound

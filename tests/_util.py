@@ -74,3 +74,18 @@ def relative_eq(a, b, epsilon, max_relative=np.finfo(np.float32).eps):
     b = np.asarray(b, np.float64)
     d = np.abs(a - b)
     return bool(np.all((d <= epsilon) | (d <= max_relative * np.maximum(np.abs(a), np.abs(b)))))
+
+
+def fmaf_f32(b, c, v) -> np.ndarray:
+    """fmaf(b, c, v) on float32 arrays, correctly rounded once (what the kernels' f32 epilogue fmaf(beta, c, fl32(alpha * acc)) computes): b * c is
+    exact in f64 (24 + 24 bits), the sum with v is made exact by TwoSum, a nonzero error term nudges an even sum one f64 ulp toward it ("round to
+    odd": 53 >= 2 * 24 + 2 bits, so the final rounding to f32 is then the single correct one)."""
+    b, c, v = np.broadcast_arrays(np.asarray(b, np.float32), np.asarray(c, np.float32), np.asarray(v, np.float32))
+    p, q = b.astype(np.float64) * c.astype(np.float64), v.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = p + q
+        bv = s - p
+        err = (p - (s - bv)) + (q - bv)
+        fix = np.isfinite(s) & (err != 0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)

@@ -16,7 +16,7 @@ WG_OK, WG_ERR_DIM_MISMATCH, WG_ERR_PRECONDITION, WG_ERR_INVALID_ARG, WG_ERR_OUT_
     WG_ERR_UNSUPPORTED, WG_ERR_NO_DEVICE, WG_ERR_WORKSPACE = range(9)
 WG_GATHER_RCCL, WG_GATHER_NONE, WG_GATHER_PEER_STAGED = 0, 2, 3  # (1 was the SDMA rect-copy engine: removed in ABI 3)
 WG_COMM_ID_BYTES, WG_IPC_HANDLE_BYTES = 128, 96
-ABI_VERSION = 4  # == WGEBRA_HIP_ABI_VERSION (checked when the library is loaded, and against the header by tests/test_abi_and_host.py)
+ABI_VERSION = 5  # == WGEBRA_HIP_ABI_VERSION (checked when the library is loaded, and against the header by tests/test_abi_and_host.py)
 WG_F32, WG_F16 = 0, 1
 WG_TUNE_F16_TILE, WG_TUNE_F16_SCHED, WG_TUNE_F32_SKINNY, WG_TUNE_F32_PANELS, WG_TUNE_F16_BALANCE, WG_TUNE_F32_MID, WG_TUNE_F32_MID_SPLIT, WG_TUNE_GEMVT_LDS, WG_TUNE_F16_CONT, WG_TUNE_RM_TR_NATIVE = range(10)
 
@@ -88,6 +88,7 @@ def _load() -> ctypes.CDLL:
         "wg_ctx_reserve_workspace": (ci, [vp, sz]),
         "wg_debug_f16_balance_plan": (ci, [ctypes.POINTER(ctypes.c_double), u32, u32, ci, ctypes.POINTER(u32), u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "wg_ctx_f16_balance_info": (ci, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "wg_debug_take_path": (ci, [vp, cp, sz]),
         "wg_ctx_set_tuning": (ci, [vp, ci, ci]),
         "wg_ctx_get_tuning": (ci, [vp, ci, ctypes.POINTER(ci)]),
         "wg_debug_spin": (ci, [vp, ctypes.c_uint32, ctypes.c_uint32, vp]),

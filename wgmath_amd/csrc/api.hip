@@ -68,6 +68,7 @@ int gemm_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, float alpha, float beta, w
     void *ws = nullptr;
     if (int rc = wg_ctx_stage_workspace(ctx, (size_t)((ae + be + ce) * mats * es), &ws)) return rc;
     char *ap = (char *)ws, *bp = ap + ae * mats * es, *cp = bp + be * mats * es;
+    wg_path(ctx, "stage%s>", !sc ? "" : beta != 0.f ? "/c=seed" : "/c");
     const uint32_t a_ld = tr ? Kp : Mp;
     wgk_mat A = { elem_ptr(m1, a.offset, dtype), a.stride, a.stride_mat }, B = { elem_ptr(m2, b.offset, dtype), b.stride, b.stride_mat };
     void *C = (void *)elem_ptr(out, o.offset, dtype);
@@ -125,6 +126,7 @@ int gemv_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, wg_buf *out, const View &o
         Vx = wgk_mat{ vp, Kp, ve };
     }
     if (so) { O = op; ldo = Op; o_batch = oe; }
+    wg_path(ctx, "stage>");
     if (int rc = wgk_gemv(ctx, tr, dtype, Op, Kp, nrhs, mats, O, ldo, o_batch, Mx, Vx)) return rc;
     if (!so) return WG_OK;
     return wgk_stage_copy(ctx, dtype, (void *)elem_ptr(out, o.offset, dtype), o.stride, o.stride_mat, rows_out, nrhs, op, Op, oe, Op, nrhs, mats);

@@ -13,7 +13,23 @@
 //                                 below it by what its data movement costs (profiles/r03_evidence.md section 9).
 #include "wg_internal.hpp"
 
+#include <cstring>
 #include <new>
+
+void wg_path(wg_ctx *ctx, const char *fmt, ...) {
+    char tag[96];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(tag, sizeof tag, fmt, ap);
+    va_end(ap);
+    std::string &s = ctx->path_log;
+    if (!s.empty() && s.back() != '>') s += ' ';
+    s += tag;
+    if (s.size() > kPathLogCap) { // keep the newest whole tags
+        const size_t cut = s.find(' ', s.size() - kPathLogCap);
+        s.erase(0, cut == std::string::npos ? s.size() - kPathLogCap : cut + 1);
+    }
+}
 
 namespace {
 
@@ -180,6 +196,18 @@ int wg_debug_mfma_ceiling(wg_ctx *ctx, double min_seconds, double *tflops, doubl
     *tflops = flops * launches / ((double)ms * 1e-3) / 1e12;
     if (clock_ghz) *clock_ghz = ghz;
     return done(WG_OK);
+}
+
+// The tags of the terminal launches since the last call (wg_path, wg_internal.hpp), then cleared: tests assert which leaf of the Gemm / Gemv launchers a call took.
+int wg_debug_take_path(wg_ctx *ctx, char *buf, size_t cap) {
+    if (!ctx) return wg_set_error(WG_ERR_INVALID_ARG, "wg_debug_take_path: ctx is NULL");
+    if (buf && cap) {
+        const size_t n = ctx->path_log.size() < cap - 1 ? ctx->path_log.size() : cap - 1;
+        memcpy(buf, ctx->path_log.data(), n);
+        buf[n] = 0;
+    }
+    ctx->path_log.clear();
+    return WG_OK;
 }
 
 } // extern "C"

@@ -1685,7 +1685,10 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
             t.tiles_n = (N + 127u) / 128u;
             t.nsplit = 1; t.k_per_split = K; t.part = nullptr;
             const uint64_t tiles_t = (uint64_t)t.tiles_m * t.tiles_n;
-            if (tiles_t <= 0x7fffffffull && nmats <= 65535u) return t128_launch(ctx, trans, dim3((uint32_t)tiles_t, nmats), t, 256);
+            if (tiles_t <= 0x7fffffffull && nmats <= 65535u) {
+                wg_path(ctx, "f16.t256x128");
+                return t128_launch(ctx, trans, dim3((uint32_t)tiles_t, nmats), t, 256);
+            }
         }
         if ((krem == 0 || K - krem >= 64u) && !panels) {
             const double out_bytes = (double)M * N * nmats * 4.0;
@@ -1734,6 +1737,7 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
                     t.part = (float *)ws;
                 }
                 if ((uint64_t)nmats * ns <= 65535) {
+                    wg_path(ctx, "f16.t128/ns=%u", ns);
                     if (int rc = t128_launch(ctx, trans, dim3((uint32_t)tiles128, nmats * ns), t)) return rc;
                     if (ns > 1) return wg_splitk_reduce(ctx, t.part, ns, M, N, nmats, WG_F16, out, out_ld, out_batch, alpha, beta);
                     return WG_OK;
@@ -1800,6 +1804,7 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
                     if (cont != 0 && applies && (cont == 1 || by_rule)) {
                         const dim3 grid((uint32_t)cus), block(256);
                         gm.sched = nullptr; gm.sched_tiles = (uint32_t)all;
+                        wg_path(ctx, "f16.cont");
                         auto go = [&](auto tr_c, auto st_c, auto a1_c) {
                             hipLaunchKernelGGL((gemm_f16_m16c_kernel<decltype(tr_c)::value, decltype(st_c)::value, decltype(a1_c)::value>), grid, block, 0, ctx->stream, gm);
                         };
@@ -1844,6 +1849,7 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
                         } else gm.bal = BalancePlan{};
                     }
                 }
+                wg_path(ctx, "f16.m16%s/ns=%u", gm.bal.on ? "bal" : dyn ? "q" : "", gm.nsplit);
                 if (trans) hipLaunchKernelGGL((gemm_f16_m16_kernel<true>), dim3(nwg, gm.nsplit * nmats), dim3(256), 0, ctx->stream, gm);
                 else hipLaunchKernelGGL((gemm_f16_m16_kernel<false>), dim3(nwg, gm.nsplit * nmats), dim3(256), 0, ctx->stream, gm);
                 return WG_OK;
@@ -1873,6 +1879,8 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
                 if (int rc = launch_tiles(g, full)) return rc; // the full rounds
                 GemmArgs gt = g; // the tail tiles, cut along K
                 gt.tile_base = full; gt.tail_tiles = tail; gt.nsplit = tail_split; gt.k_per_split = tail_kps; gt.part = (float *)ws;
+                wg_path(ctx, "f16.m16tail/ns=%u", tail_split);
+                wg_path(ctx, "f16.tail_reduce");
                 if (trans) hipLaunchKernelGGL((gemm_f16_m16_kernel<true>), dim3(tail, tail_split), dim3(256), 0, ctx->stream, gt);
                 else hipLaunchKernelGGL((gemm_f16_m16_kernel<false>), dim3(tail, tail_split), dim3(256), 0, ctx->stream, gt);
                 hipLaunchKernelGGL(gemm_f16_tail_reduce, dim3(tail, 64), dim3(256), 0, ctx->stream, gt);
@@ -1913,6 +1921,7 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
         void *ws = nullptr;
         if (int rc = wg_ctx_pad_workspace(ctx, (size_t)((a_sz + b_sz + c_sz) * nmats * sizeof(_Float16)) + 16, &ws)) return rc;
         _Float16 *ap = (_Float16 *)ws, *bp = ap + a_sz * nmats, *cp = bp + b_sz * nmats;
+        wg_path(ctx, "f16.pad%s>", c_ok ? "" : beta != 0.f ? "/c=seed" : "/c");
         wgk_mat a2 = m1, b2 = m2;
         if (!a_ok) { // op(A) is M x K: stored M x K or, transposed, K x M
             if (trans) { if (int rc = pad_copy(ctx, ap, Kp, a_sz, Kp, Mp, (const _Float16 *)m1.ptr, m1.ld, m1.batch, K, M, nmats)) return rc; }
@@ -1933,6 +1942,7 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
         g.tiles_n = (N + 63) / 64;
         g.nsplit = 1; g.k_per_split = K; g.part = nullptr;
         if (g.tiles_n > 65535) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: N too large for the generic f16 path");
+        wg_path(ctx, "f16.generic");
         if (int rc = generic_launch(ctx, trans, dim3(g.tiles_m, g.tiles_n, nmats), g)) return rc;
     }
     WG_HIP_TRY(hipGetLastError());

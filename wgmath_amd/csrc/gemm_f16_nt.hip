@@ -255,6 +255,7 @@ static int nt_launch(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t n
         if (tt > 0x7fffffffull) return WG_ERR_UNSUPPORTED;
         return t128_launch_nt(ctx, dim3((uint32_t)tt, nmats), t, tall ? 256 : 128);
     }
+    wg_path(ctx, "f16.nt");
     hipLaunchKernelGGL(gemm_f16_nt_kernel, dim3((uint32_t)tiles, nmats), dim3(256), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;

@@ -603,6 +603,7 @@ int wgk_gemm_f32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
         void *ws = nullptr;
         if (int rc = wg_ctx_pad_workspace(ctx, (size_t)((at_elems + ct_elems) * nmats * sizeof(float)), &ws)) return rc;
         float *at = (float *)ws, *ct = at + at_elems * nmats;
+        wg_path(ctx, "f32.fewrow>");
         wgk_mat a2 = m1; // K x M, column m contiguous in k
         if (!trans) {
             if (int rc = wgk_transpose(ctx, WG_F32, M, K, nmats, m1.ptr, m1.ld, m1.batch, at, K, at_elems)) return rc;
@@ -622,6 +623,7 @@ int wgk_gemm_f32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
         void *ws = nullptr;
         if (int rc = wg_ctx_pad_workspace(ctx, (size_t)((at_elems + ct_elems) * nmats * sizeof(float)), &ws)) return rc;
         float *at = (float *)ws, *ct = at + at_elems * nmats;
+        wg_path(ctx, "f32.fewrow>");
         wgk_mat a2 = m1; // K x M, column m contiguous in k
         if (!trans) {
             if (int rc = wgk_transpose(ctx, WG_F32, M, K, nmats, m1.ptr, m1.ld, m1.batch, at, K, at_elems)) return rc;
@@ -834,6 +836,9 @@ int wgk_gemm_f32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
         if (int rc = wg_ctx_workspace(ctx, (size_t)n * r * BM * BN * sizeof(float), &ws)) return rc;
         const uint32_t full = (uint32_t)(tiles * nmats) - r;
         if (nmats > 1) g.flat_tiles = (uint32_t)tiles; // the ids run through the batch
+        wg_path(ctx, "f32.big/ns=1");
+        wg_path(ctx, "f32.bigtail/ns=%u", n);
+        wg_path(ctx, "f32.tail_reduce");
         if (trans) hipLaunchKernelGGL(gemm_f32_kernel<true>, dim3(full, 1), block, 0, ctx->stream, g);
         else hipLaunchKernelGGL(gemm_f32_kernel<false>, dim3(full, 1), block, 0, ctx->stream, g);
         GemmArgs gt = g;
@@ -845,6 +850,7 @@ int wgk_gemm_f32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
         WG_HIP_TRY(hipGetLastError());
         return WG_OK;
     }
+    wg_path(ctx, "f32.big/ns=%u", nsplit);
     if (trans) hipLaunchKernelGGL(gemm_f32_kernel<true>, grid, block, 0, ctx->stream, g);
     else hipLaunchKernelGGL(gemm_f32_kernel<false>, grid, block, 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
@@ -875,6 +881,7 @@ int wgk_gemm_f32_nt(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nm
     g.dma_ok = ((uint64_t)a_mcontig.ld * 16u * 4u < (1ull << 31)) && ((uint64_t)b_ncontig.ld * 16u * 4u < (1ull << 31)) ? 1u : 0u;
     const uint64_t tiles = (uint64_t)g.tiles_m * g.tiles_n;
     if (tiles > 0x7fffffffull) return WG_ERR_UNSUPPORTED;
+    wg_path(ctx, "f32.nt");
     hipLaunchKernelGGL((gemm_f32_kernel<false, true>), dim3((uint32_t)tiles, nmats), dim3(kThreads), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;

@@ -614,6 +614,7 @@ int wgk_gemm_f32_mid(wg_ctx *ctx, bool trans, int bm, int bn, uint32_t M, uint32
     g.tiles_n = (N + (uint32_t)bn - 1) / (uint32_t)bn;
     if ((uint64_t)g.tiles_m * g.tiles_n > 0x7fffffffull) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: too many tiles");
     int rc = WG_ERR_INVALID_ARG;
+    wg_path(ctx, "f32.mid%dx%d/ns=%u", bm, bn, g.nsplit);
     if (bm == 128 && bn == 128) rc = launch<2, 2>(ctx, trans, nmats, g);
     else if (bm == 128 && bn == 64) rc = launch<2, 1>(ctx, trans, nmats, g);
     else if (bm == 64 && bn == 128) rc = launch<1, 2>(ctx, trans, nmats, g);

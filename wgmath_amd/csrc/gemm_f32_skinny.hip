@@ -428,6 +428,8 @@ int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_
     g.a_nt = (npanels == 1 && (uint64_t)M * K * 4u >= (384ull << 20)) ? 1u : 0u; // read once, and no use to the 256 MiB Infinity Cache (tr_dma_streamed)
     const dim3 grid(row_blocks, ns, nmats * npanels);
     const bool w16 = WG_SKINNY_W16 && N <= 16u && npanels == 1u;
+    if (npanels > 1u) wg_path(ctx, "f32.skinny%s/p=%u,ns=%u", m2_kmajor || out_row_stride != 1u ? "T" : "", npanels, ns);
+    else wg_path(ctx, "f32.skinny%s/ns=%u", m2_kmajor || out_row_stride != 1u ? "T" : "", ns);
     if (m2_kmajor) { // GemmTr only (the few-row route)
         if (w16) hipLaunchKernelGGL((gemm_f32_skinny_kernel<true, 1, true, true>), grid, dim3(256), 0, ctx->stream, g);
         else if (N <= 32) hipLaunchKernelGGL((gemm_f32_skinny_kernel<true, 1, true>), grid, dim3(256), 0, ctx->stream, g);
@@ -474,6 +476,7 @@ int wgk_gemm_f16_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_
     g.part = (float *)ws; g.M = M; g.N = N; g.K = K; g.nsplit = ns; g.k_per_split = kps; g.npanels = 1;
     g.rot = (uint64_t)(ns > 1 ? kps : K) * N * 2u <= (256u << 10) ? 1u : 0u;
     g.a_nt = (uint64_t)M * K * 2u >= (384ull << 20) ? 1u : 0u;
+    wg_path(ctx, "f16.skinny/ns=%u", ns);
     hipLaunchKernelGGL((gemm_f32_skinny_kernel<true, 1, false, true, _Float16>), dim3(row_blocks, ns, nmats), dim3(256), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
     if (ns == 1) return WG_OK;

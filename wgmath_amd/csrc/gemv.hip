@@ -923,7 +923,9 @@ static bool uses_t_lds(const wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_
 int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats,
              void *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v) {
     if (rows_out == 0 || nrhs == 0 || nmats == 0) return WG_OK;
+    wg_path(ctx, "gemv>");
     if (uses_t_lds(ctx, trans, rows_out, k, nrhs, nmats, dtype == WG_F16 ? 2u : 4u)) {
+        wg_path(ctx, "gemv.tlds");
         return gemv_t_lds_launch<float>(ctx, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
     }
     if (dtype == WG_F16) {
@@ -932,6 +934,7 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
         // Gemm with few columns: the f16 Gemm kernels take any column count (one pass over the matrix on the matrix cores).
         if (nrhs > (uint32_t)kMaxRhs || few_rhs_as_gemm(trans, true, rows_out, k, nrhs, 2u))
             return wgk_gemm_f16(ctx, trans, rows_out, nrhs, k, nmats, (__half *)out, out_ld, out_batch, m, v, 1.f, 0.f);
+        wg_path(ctx, "f16.gemv");
         return gemv_launch<_Float16>(ctx, trans, rows_out, k, nrhs, nmats, (_Float16 *)out, out_ld, out_batch, m, v);
     }
     // 9 .. 64 right-hand sides are a Gemm with few columns: one pass over the matrix on the matrix cores (gemm_f32_skinny.hip) instead of
@@ -939,6 +942,7 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
     if ((nrhs > (uint32_t)kMaxRhs || few_rhs_as_gemm(trans, false, rows_out, k, nrhs, 4u)) && nrhs <= 64u && rows_out >= 512u && k >= 128u &&
         (uint64_t)m.ld * 32u * 4u < (1ull << 31) && (uint64_t)v.ld * 64u * 4u < (1ull << 31))
         return wgk_gemm_f32_skinny(ctx, trans, rows_out, nrhs, k, nmats, (float *)out, out_ld, out_batch, m, v, 1.f, 0.f);
+    wg_path(ctx, "f32.gemv");
     return gemv_launch<float>(ctx, trans, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
 }
 

@@ -83,14 +83,15 @@ struct AnyArgs {
     uintptr_t m; uint32_t ldm; uint64_t m_batch; // elements
     uintptr_t v; uint32_t ldv; uint64_t v_batch;
     uintptr_t out; uint32_t ldo; uint64_t o_batch;
-    float *part;       // f32 partials [matrix * rhs][split][out_len] when nsplit > 1
+    float *part;       // f32 partials [matrix * rhs - zbase][split][out_len] when nsplit > 1 (the launch's own chunk of them)
     uint32_t R, C;     // the matrix view: R rows (contiguous), C columns
     uint32_t nrhs, nsplit, per_split; // per_split: columns (N) / rows (T) of one split
+    uint32_t zbase;    // (matrix, right-hand side) pairs are numbered z * nrhs + y; a launch takes the <= 65535 of them from zbase on (grid.z / grid.y)
 };
 
 template <typename T>
 __device__ __forceinline__ void store_out(const AnyArgs &a, uint32_t z, uint32_t y, uint32_t split, uint32_t out_len, uint32_t i, float x) {
-    if (a.part) a.part[((uint64_t)(z * a.nrhs + y) * a.nsplit + split) * out_len + i] = x;
+    if (a.part) a.part[((uint64_t)(z * a.nrhs + y - a.zbase) * a.nsplit + split) * out_len + i] = x;
     else reinterpret_cast<T *>(a.out)[z * a.o_batch + (uint64_t)y * a.ldo + i] = (T)x;
 }
 
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(kThreads) void gemv_any_n_kernel(AnyArgs a) {
     constexpr int E = Elt<T>::E, ES = Elt<T>::ES, U = WG_ANY_NU;
     __shared__ float part[kWaves][E][64];
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t z = blockIdx.z / a.nrhs, y = blockIdx.z % a.nrhs;
+    const uint32_t z = (a.zbase + blockIdx.z) / a.nrhs, y = (a.zbase + blockIdx.z) % a.nrhs;
     const uint32_t r0 = (blockIdx.x * 64u + lane) * E;
     const uint32_t c_begin = blockIdx.y * a.per_split, c_end = min(a.C, c_begin + a.per_split);
     const uint32_t per_wave = (c_end - c_begin + kWaves - 1u) / kWaves;
@@ -149,7 +150,7 @@ template <typename T, bool NT>
 __global__ __launch_bounds__(kThreads) void gemv_any_t_kernel(AnyArgs a) {
     constexpr int E = Elt<T>::E, ES = Elt<T>::ES, CW = 4;
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t z = blockIdx.z / a.nrhs, y = blockIdx.z % a.nrhs;
+    const uint32_t z = (a.zbase + blockIdx.z) / a.nrhs, y = (a.zbase + blockIdx.z) % a.nrhs;
     const uint32_t c0 = (blockIdx.x * kWaves + wave) * CW;
     if (c0 >= a.C) return;
     const uint32_t r_begin = blockIdx.y * a.per_split, r_end = min(a.R, r_begin + a.per_split);
@@ -183,7 +184,7 @@ __global__ __launch_bounds__(kThreads) void gemv_any_t_kernel(AnyArgs a) {
 // out[i] = sum over the splits, in order. grid = (blocks of 256 outputs, matrices * right-hand sides)
 template <typename T>
 __global__ __launch_bounds__(kThreads) void gemv_any_combine_kernel(AnyArgs a, uint32_t out_len) {
-    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, z = blockIdx.y / a.nrhs, y = blockIdx.y % a.nrhs;
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x, z = (a.zbase + blockIdx.y) / a.nrhs, y = (a.zbase + blockIdx.y) % a.nrhs;
     if (i >= out_len) return;
     const float *p = a.part + (uint64_t)blockIdx.y * a.nsplit * out_len + i;
     float s = p[0];
@@ -196,13 +197,14 @@ int launch_any(wg_ctx *ctx, bool trans, uint32_t R, uint32_t C, uint32_t nrhs, u
     constexpr uint32_t E = Elt<T>::E;
     const uint32_t cus = ctx->compute_units > 0 ? (uint32_t)ctx->compute_units : 256u;
     const uint64_t gz = (uint64_t)nmats * nrhs;
-    if (gz > 65535u) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemv: matrices x right-hand sides = %llu exceeds 65535 on the path for views that are not vec4-aligned", (unsigned long long)gz);
+    if (gz > 0xffffffffull) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemv: matrices x right-hand sides = %llu exceeds 2^32 - 1", (unsigned long long)gz);
+    const uint32_t zchunk = gz < 65535u ? (uint32_t)gz : 65535u; // grid.z (grid.y of the combine pass) per launch: the pairs go in chunks of up to 65535
     const uint32_t out_len = trans ? C : R;
     AnyArgs a;
     a.m = (uintptr_t)m.ptr; a.ldm = m.ld; a.m_batch = m.batch;
     a.v = (uintptr_t)v.ptr; a.ldv = v.ld; a.v_batch = v.batch;
     a.out = (uintptr_t)out; a.ldo = out_ld; a.o_batch = out_batch;
-    a.R = R; a.C = C; a.nrhs = nrhs; a.part = nullptr;
+    a.R = R; a.C = C; a.nrhs = nrhs; a.part = nullptr; a.zbase = 0;
     // ~per_cu workgroups per CU; a split is whole 64-column chunks (N) / whole 64 E-row steps (T)
     const uint32_t gx = trans ? (C + 4u * kWaves - 1u) / (4u * kWaves) : (R + 64u * E - 1u) / (64u * E);
     const uint32_t unit = trans ? 64u * E : 64u * kWaves, len = trans ? R : C, units = (len + unit - 1u) / unit;
@@ -216,20 +218,27 @@ int launch_any(wg_ctx *ctx, bool trans, uint32_t R, uint32_t C, uint32_t nrhs, u
     a.nsplit = nsplit;
     if (nsplit > 1u) {
         void *ws = nullptr;
-        if (int rc = wg_ctx_workspace(ctx, (size_t)gz * nsplit * out_len * sizeof(float), &ws)) return rc;
+        if (int rc = wg_ctx_workspace(ctx, (size_t)zchunk * nsplit * out_len * sizeof(float), &ws)) return rc; // (one chunk's partials: the chunks run in stream order)
         a.part = (float *)ws;
     }
-    const dim3 grid(gx, nsplit, (uint32_t)gz), block(kThreads);
     const bool nt = (uint64_t)R * C * sizeof(T) >= (512ull << 20);
-    if (trans) {
-        if (nt) hipLaunchKernelGGL((gemv_any_t_kernel<T, true>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((gemv_any_t_kernel<T, false>), grid, block, 0, ctx->stream, a);
-    } else if (nt) hipLaunchKernelGGL((gemv_any_n_kernel<T, true>), grid, block, 0, ctx->stream, a);
-    else hipLaunchKernelGGL((gemv_any_n_kernel<T, false>), grid, block, 0, ctx->stream, a);
-    WG_HIP_TRY(hipGetLastError());
-    if (nsplit > 1u) {
-        hipLaunchKernelGGL(gemv_any_combine_kernel<T>, dim3((out_len + kThreads - 1u) / kThreads, (uint32_t)gz), block, 0, ctx->stream, a, out_len);
+    const uint32_t nchunks = (uint32_t)((gz + zchunk - 1u) / zchunk);
+    if (nchunks > 1u) wg_path(ctx, "gemv_any/ns=%u,chunks=%u", nsplit, nchunks);
+    else wg_path(ctx, "gemv_any/ns=%u", nsplit);
+    for (uint64_t base = 0; base < gz; base += zchunk) {
+        a.zbase = (uint32_t)base;
+        const uint32_t nz = gz - base < zchunk ? (uint32_t)(gz - base) : zchunk;
+        const dim3 grid(gx, nsplit, nz), block(kThreads);
+        if (trans) {
+            if (nt) hipLaunchKernelGGL((gemv_any_t_kernel<T, true>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((gemv_any_t_kernel<T, false>), grid, block, 0, ctx->stream, a);
+        } else if (nt) hipLaunchKernelGGL((gemv_any_n_kernel<T, true>), grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((gemv_any_n_kernel<T, false>), grid, block, 0, ctx->stream, a);
         WG_HIP_TRY(hipGetLastError());
+        if (nsplit > 1u) {
+            hipLaunchKernelGGL(gemv_any_combine_kernel<T>, dim3((out_len + kThreads - 1u) / kThreads, nz), block, 0, ctx->stream, a, out_len);
+            WG_HIP_TRY(hipGetLastError());
+        }
     }
     return WG_OK;
 }

@@ -74,6 +74,7 @@ int wg_splitk_reduce(wg_ctx *ctx, const float *part, uint32_t nsplit, uint32_t M
     if ((uint64_t)(M / 4u) * N >= (1ull << 32) - 65536ull * 256ull) return wg_set_error(WG_ERR_UNSUPPORTED, "split-K reduce: output of more than 2^34 elements");
     const uint64_t blocks = ((uint64_t)(M / 4u) * N + 255u) / 256u;
     const dim3 grid((uint32_t)(blocks < 65536u ? (blocks ? blocks : 1u) : 65536u), 1, nmats), block(256); // (larger outputs: grid-stride trips)
+    wg_path(ctx, "splitk.reduce/ns=%u", nsplit);
     if (dtype == WG_F32) hipLaunchKernelGGL(splitk_reduce_kernel<float>, grid, block, 0, ctx->stream, part, nsplit, M, N, (float *)out, ldc, c_batch, alpha, beta);
     else hipLaunchKernelGGL(splitk_reduce_kernel<_Float16>, grid, block, 0, ctx->stream, part, nsplit, M, N, (_Float16 *)out, ldc, c_batch, alpha, beta);
     WG_HIP_TRY(hipGetLastError());
@@ -84,6 +85,7 @@ int wg_splitk_reduce_strided(wg_ctx *ctx, const float *part, uint32_t nsplit, ui
                              uint32_t row_stride, uint32_t col_stride, uint64_t c_batch, float alpha) {
     if (nmats > 65535) return wg_set_error(WG_ERR_UNSUPPORTED, "split-K reduce: more than 65535 matrices");
     const dim3 grid((M + 255u) / 256u, N < 65535u ? N : 65535u, nmats), block(256);
+    wg_path(ctx, "splitk.reduceT/ns=%u", nsplit);
     hipLaunchKernelGGL(splitk_reduce_strided_kernel, grid, block, 0, ctx->stream, part, nsplit, M, N, out, row_stride, col_stride, c_batch, alpha);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;

@@ -36,6 +36,7 @@ int wgk_transpose(wg_ctx *ctx, wg_dtype dtype, uint32_t rows, uint32_t cols, uin
     if (rows == 0 || cols == 0 || nmats == 0) return WG_OK;
     const dim3 grid((rows + 63u) / 64u, (cols + 63u) / 64u, nmats), block(256);
     if (grid.y > 65535u || grid.z > 65535u) return wg_set_error(WG_ERR_UNSUPPORTED, "transpose: matrix too wide or too many matrices for one launch");
+    wg_path(ctx, "transpose");
     if (dtype == WG_F32)
         hipLaunchKernelGGL(transpose_kernel<float>, grid, block, 0, ctx->stream, (const float *)src, ld_src, src_batch, (float *)dst, ld_dst,
                            dst_batch, rows, cols);

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <functional>
 #include <memory>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -71,6 +72,7 @@ struct wg_ctx {
     // kernel timing out on a peer): checked -- reported once, then cleared -- by wg_ctx_sync, wg_buf_read and the communicator's calls
     struct AsyncError { uint32_t *word; const char *what; uint32_t *dev_word; };
     std::vector<AsyncError> async_errors;
+    std::string path_log; // wg_path: tags of the terminal launches since the last wg_debug_take_path (tests read which leaf a call took)
 };
 // A destroy call that arrives while THIS THREAD records a command buffer (hipStreamBeginCapture, thread-local mode) must not run now: hipFree /
 // hipStreamSynchronize from the capturing thread are prohibited and invalidate the capture. It happens -- a garbage-collected host object
@@ -106,6 +108,12 @@ struct wg_timestamps {
     std::vector<uint8_t> written; // slot i holds a recorded event (a slot can be reserved -- next_query_indices -- and written later, or never)
     uint32_t len = 0;
 };
+
+// Which leaf of the launchers' dispatch trees a call took (host-side only): appends a short tag -- "f32.big/ns=4", "f16.m16tail/ns=3" -- to ctx->path_log,
+// space-separated; a tag that ends in '>' is a wrapper (staging, padding, transposed form) and the next tag follows it directly: "f16.pad>f16.t128/ns=1". The log
+// keeps its last kPathLogCap bytes (whole tags), so a context that nobody reads does not grow it. wg_debug_take_path (debug.hip) hands it out and clears it.
+constexpr size_t kPathLogCap = 480;
+void wg_path(wg_ctx *ctx, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // ---- error plumbing -------------------------------------------------------------------------------
 int wg_set_error(int status, const char *fmt, ...) __attribute__((format(printf, 2, 3)));

@@ -371,6 +371,13 @@ class GpuInstance:
         check(lib.wg_ctx_f16_balance_info(self._ctx.handle, rel, ctypes.byref(valid), ctypes.byref(upd), ctypes.byref(n)))
         return {"rel": [round(float(v), 4) for v in rel], "valid": bool(valid.value), "updates": upd.value, "balanced_launches": n.value}
 
+    def take_path(self) -> str:
+        """wg_debug_take_path: the tags of the Gemm / Gemv launches since the last call ("f32.big/ns=4 splitk.reduce/ns=4"), then cleared -- which leaf a
+        call took (tests)."""
+        buf = ctypes.create_string_buffer(1024)
+        check(lib.wg_debug_take_path(self._ctx.handle, buf, len(buf)))
+        return buf.value.decode()
+
     def get_tuning(self, knob: str) -> int:
         v = ctypes.c_int()
         check(lib.wg_ctx_get_tuning(self._ctx.handle, self._TUNING[knob], ctypes.byref(v)))
