@@ -172,9 +172,12 @@ int wg_debug_spin(wg_ctx *ctx, uint32_t blocks, uint32_t usec, wg_buf *start_tic
 int wg_debug_clock_begin(wg_ctx *ctx);
 int wg_debug_clock_end(wg_ctx *ctx, double *ghz_mean, double *ghz_min, double *ghz_max, double *seconds);
 int wg_debug_mfma_ceiling(wg_ctx *ctx, double min_seconds, double *tflops, double *clock_ghz);
-/* Which leaves of the Gemm / Gemv launchers' dispatch trees ran since the last call (tests): one short tag per terminal launch, space-separated --
+/* Which leaves of the Gemm / Gemv / Reduce launchers' dispatch trees ran since the last call (tests): one short tag per terminal launch, space-separated --
  * "f32.big/ns=4 splitk.reduce/ns=4", "f16.cont", "f16.pad/c=seed>f16.t128/ns=1" (a tag ending in '>' wraps the next one: staging, padding, transposed
- * forms). Equal logs mean the same kernels in the same summation order. Host-side bookkeeping only; the context keeps the newest few hundred bytes.
+ * forms). Gemv names its kernel instance: "gemv> f32.gemv gemv.n/t=4,ns=3 gemv.combine/ns=3", "gemv.small/rl=8", "gemv.t/t=8,ns=1",
+ * "gemv.tcols/e=8,u=4,v=2,ns=1" (elements per load, loads in flight, right-hand sides), "gemv.tlds/nr=4,c=2,th=1024", "gemv.small_reduce/rl=4",
+ * "gemv_reduce.two>" (wg_gemv_reduce as Gemv, then Reduce), "gemv_any/t,ns=2" (views the vec4 kernels cannot take); Reduce: "reduce.long",
+ * "reduce.rows4/al=1" (al: the aligned vec4 instance), "reduce.fast/np=64". Equal logs mean the same kernels in the same summation order. Host-side bookkeeping only; the context keeps the newest few hundred bytes.
  * Copies the log into buf (NUL-terminated, truncated to cap - 1 bytes) and clears it; buf may be NULL to just clear it. */
 int wg_debug_take_path(wg_ctx *ctx, char *buf, size_t cap);
 

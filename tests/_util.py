@@ -89,3 +89,36 @@ def fmaf_f32(b, c, v) -> np.ndarray:
         fix = np.isfinite(s) & (err != 0) & ((s.view(np.int64) & 1) == 0)
         s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
         return s.astype(np.float32)
+
+
+def special_product(A, B, dtype):
+    """op(A) B per matrix, rounded once to `dtype`, for operands whose finite part multiplies exactly (integers with every partial sum below 2^24 in
+    magnitude: any summation order and any split of K give the same f32 sum). A is M x K x mats, B is K x N x mats, in float64; they may hold +-Inf and
+    NaN. The result is the exact product over the k whose column of A and row of B are finite, plus in f64 the outer product A[:, k] x B[k, :] of every
+    other k (Inf * 0 = NaN, Inf + -Inf = NaN: IEEE, and order-free once the finite part is exact), then one rounding. A negative zero becomes +0: the
+    sign of an exact zero sum depends on where an accumulator starts, which the contract leaves open (tests compare zeros as one class)."""
+    A, B = np.asarray(A, np.float64), np.asarray(B, np.float64)
+    fin = np.isfinite(A).all(axis=0) & np.isfinite(B).all(axis=1)  # K x mats
+    out = np.zeros((A.shape[0], B.shape[1], A.shape[2]), np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for z in range(A.shape[2]):
+            ks = np.flatnonzero(fin[:, z])
+            out[:, :, z] = A[:, ks, z] @ B[ks, :, z]
+            for k in np.flatnonzero(~fin[:, z]):
+                out[:, :, z] += np.outer(A[:, k, z], B[k, :, z])
+        return (out + 0.0).astype(dtype)
+
+
+def assert_same_class_bits(got, want, what=""):
+    """Bit equality with NaN compared as a class (any payload) and zeros as one class; Inf with its sign."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, got.shape, want.shape)
+    gn, wn = np.isnan(got), np.isnan(want)
+    ut = np.uint32 if got.dtype.itemsize == 4 else np.uint16
+    g = np.where(got == 0, 0, got).astype(got.dtype).view(ut)
+    w = np.where(want == 0, 0, want).astype(want.dtype).view(ut)
+    bad = (gn != wn) | (~gn & ~wn & (g != w))
+    if bad.any():
+        i = np.flatnonzero(bad.ravel())
+        raise AssertionError(f"{what}: {i.size} of {got.size} elements differ; first at {np.unravel_index(i[0], got.shape)}: got {got.ravel()[i[0]]!r}, "
+                             f"expected {want.ravel()[i[0]]!r}")

@@ -295,6 +295,7 @@ int wg_gemv_reduce(wg_ctx *ctx, wg_gemv_variant variant, wg_reduce_op op, wg_dty
         const int rc = wgk_gemv_small_reduce(ctx, (int)op, out_rows, mm.cols, (float *)ws, M, V, ctx->flags, (float *)result->ptr);
         if (rc != WG_ERR_UNSUPPORTED) return rc;
     }
+    wg_path(ctx, "gemv_reduce.two>");
     wg_buf tmp;
     tmp.ctx = ctx; tmp.ptr = ws; tmp.bytes = (size_t)(out_rows ? out_rows : 4) * sizeof(float); tmp.usage = 0; tmp.owned = false; tmp.host_pinned = false;
     wg_view_shape os;

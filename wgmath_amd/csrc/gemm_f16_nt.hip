@@ -253,6 +253,7 @@ static int nt_launch(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t n
         t.part = nullptr;
         const uint64_t tt = (uint64_t)t.tiles_m * t.tiles_n;
         if (tt > 0x7fffffffull) return WG_ERR_UNSUPPORTED;
+        wg_path(ctx, "f16.t128nc/tm=%d", tall ? 256 : 128);
         return t128_launch_nt(ctx, dim3((uint32_t)tt, nmats), t, tall ? 256 : 128);
     }
     wg_path(ctx, "f16.nt");

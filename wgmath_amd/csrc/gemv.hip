@@ -758,6 +758,7 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
     if (uses_small_kernel(cus, trans, rows_out, k, nrhs, nsplit)) {
         a.part = nullptr; a.ld_dst = out_ld; a.dst_split = 0; a.dst_batch = out_batch;
         const int rl = gemv_small_rl(rows_out);
+        wg_path(ctx, "gemv.small/rl=%d", rl);
         const dim3 sg(ceil_div(rows_out, 4u * (uint32_t)rl), nrhs, nmats);
         if (rl == 8) hipLaunchKernelGGL((gemv_n_small_kernel<8, T>), sg, dim3(kThreads), 0, ctx->stream, a);
         else if (rl == 4) hipLaunchKernelGGL((gemv_n_small_kernel<4, T>), sg, dim3(kThreads), 0, ctx->stream, a);
@@ -776,6 +777,9 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
         if constexpr (sizeof(T) == 2)
             wide = (uintptr_t)a.m % 16 == 0 && (uintptr_t)a.v % 16 == 0 && a.ldm % 8 == 0 && a.k_per_split % 8 == 0 && (nmats == 1 || (a.m_batch % 8 == 0 && a.v_batch % 8 == 0)) &&
                    (nrhs == 1 || a.ldv % 8 == 0);
+        // (the tag names the instance the branches below launch: elements per load, loads in flight, right-hand sides)
+        const int te = wide ? 8 : 4, tu = nrhs == 2 || t_cols_u4(a.k_per_split, (uint32_t)te) ? 4 : WG_GEMVT_U;
+        wg_path(ctx, "gemv.tcols/e=%d,u=%d,v=%u,ns=%u", te, tu, nrhs, nsplit);
         if (nrhs == 2) { // (uses_t_cols2)
             if constexpr (sizeof(T) == 2) {
                 if (wide) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, 4, 2>), grid, block, 0, ctx->stream, a);
@@ -790,11 +794,13 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
         else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4>), grid, block, 0, ctx->stream, a);
     }
     else if (trans) {
+        wg_path(ctx, "gemv.t/t=%d,ns=%u", tile, nsplit);
         if (tile == 1) hipLaunchKernelGGL((gemv_t_kernel<1, T>), grid, block, 0, ctx->stream, a);
         else if (tile == 2) hipLaunchKernelGGL((gemv_t_kernel<2, T>), grid, block, 0, ctx->stream, a);
         else if (tile == 4) hipLaunchKernelGGL((gemv_t_kernel<4, T>), grid, block, 0, ctx->stream, a);
         else hipLaunchKernelGGL((gemv_t_kernel<8, T>), grid, block, 0, ctx->stream, a);
     } else {
+        wg_path(ctx, "gemv.n/t=%d,ns=%u", tile, nsplit);
         if (tile == 1) hipLaunchKernelGGL((gemv_n_kernel<1, T>), grid, block, 0, ctx->stream, a);
         else if (tile == 2) hipLaunchKernelGGL((gemv_n_kernel<2, T>), grid, block, 0, ctx->stream, a);
         else if (tile == 4) hipLaunchKernelGGL((gemv_n_kernel<4, T>), grid, block, 0, ctx->stream, a);
@@ -802,6 +808,7 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
     }
     WG_HIP_TRY(hipGetLastError());
     if (nsplit > 1) {
+        wg_path(ctx, "gemv.combine/ns=%u", nsplit);
         hipLaunchKernelGGL(gemv_combine_kernel<T>, dim3(ceil_div(rows_out / 4u, 4u), nrhs, nmats), block, 0, ctx->stream, a.part, nsplit, rows_out, nrhs, out,
                            out_ld, out_batch);
         WG_HIP_TRY(hipGetLastError());
@@ -872,6 +879,7 @@ static int gemv_t_lds_launch(wg_ctx *ctx, uint32_t rows_out, uint32_t k, uint32_
     const uint32_t cus = (uint32_t)(ctx->compute_units > 0 ? ctx->compute_units : 256);
     const TLdsPlan pl = gemv_t_lds_plan(cus, rows_out, k, (uint32_t)tile);
     const dim3 grid(pl.grid, 1, nmats);
+    wg_path(ctx, "gemv.tlds/nr=%d,c=%d,th=%d", tile, pl.cols, pl.threads);
     // hipFuncAttributeMaxDynamicSharedMemorySize once per context (= per device and stream) and instantiation: bit = 5 * tile index + shape index
 #define WG_T_LDS(NR, COLS, THREADS, SHAPE)                                                                                                     \
     do {                                                                                                                                       \
@@ -925,7 +933,6 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
     if (rows_out == 0 || nrhs == 0 || nmats == 0) return WG_OK;
     wg_path(ctx, "gemv>");
     if (uses_t_lds(ctx, trans, rows_out, k, nrhs, nmats, dtype == WG_F16 ? 2u : 4u)) {
-        wg_path(ctx, "gemv.tlds");
         return gemv_t_lds_launch<float>(ctx, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
     }
     if (dtype == WG_F16) {
@@ -958,6 +965,7 @@ int wgk_gemv_small_reduce(wg_ctx *ctx, int op, uint32_t rows_out, uint32_t k, fl
     a.out = y; a.part = nullptr; a.ld_dst = rows_out; a.dst_split = 0; a.dst_batch = 0;
     const int rl = gemv_small_rl(rows_out);
     const dim3 grid(ceil_div(rows_out, 4u * (uint32_t)rl)), block(kThreads);
+    wg_path(ctx, "gemv.small_reduce/rl=%d", rl);
 #define WG_SMALL_REDUCE(OP)                                                                                                          \
     do {                                                                                                                             \
         if (rl == 8) hipLaunchKernelGGL((gemv_n_small_reduce_kernel<OP, 8>), grid, block, 0, ctx->stream, a, counter, result);        \

@@ -223,8 +223,8 @@ int launch_any(wg_ctx *ctx, bool trans, uint32_t R, uint32_t C, uint32_t nrhs, u
     }
     const bool nt = (uint64_t)R * C * sizeof(T) >= (512ull << 20);
     const uint32_t nchunks = (uint32_t)((gz + zchunk - 1u) / zchunk);
-    if (nchunks > 1u) wg_path(ctx, "gemv_any/ns=%u,chunks=%u", nsplit, nchunks);
-    else wg_path(ctx, "gemv_any/ns=%u", nsplit);
+    if (nchunks > 1u) wg_path(ctx, "gemv_any/%s,ns=%u,chunks=%u", trans ? "t" : "n", nsplit, nchunks);
+    else wg_path(ctx, "gemv_any/%s,ns=%u", trans ? "t" : "n", nsplit);
     for (uint64_t base = 0; base < gz; base += zchunk) {
         a.zbase = (uint32_t)base;
         const uint32_t nz = gz - base < zchunk ? (uint32_t)(gz - base) : zchunk;

@@ -198,12 +198,14 @@ int launch(wg_ctx *ctx, const T *base, uint32_t n, uint32_t ncols, uint32_t nmat
     if (nvec64 > 0x7fffffffull) return wg_set_error(WG_ERR_UNSUPPORTED, "Reduce: more than 2^31 vectors in one call");
     const uint32_t nvec = (uint32_t)nvec64;
     if (n >= 65536u && nvec <= 256u) { // long vectors, fewer than there are CUs: one 8-wave workgroup each (f16 too since round 6: 2^22 elements 900 -> ~300 us)
+        wg_path(ctx, "reduce.long");
         hipLaunchKernelGGL((reduce_long<OP, T>), dim3(nvec), dim3(kLongThreads), 0, ctx->stream, base, n, ncols, nvec, stride, stride_mat, results);
         WG_HIP_TRY(hipGetLastError());
         return WG_OK;
     }
     const uint32_t per_block = kThreads / 32;
     const bool aligned = ((uintptr_t)base % (4 * sizeof(T)) == 0) && (nvec == 1 || ((stride % 4 == 0) && (nmats == 1 || stride_mat % 4 == 0)));
+    wg_path(ctx, "reduce.rows4/al=%d", aligned ? 1 : 0);
     if (aligned) hipLaunchKernelGGL((reduce_rows4<OP, T, true>), dim3((nvec + per_block - 1) / per_block), dim3(kThreads), 0, ctx->stream, base, n, ncols, nvec, stride, stride_mat, results);
     else hipLaunchKernelGGL((reduce_rows4<OP, T, false>), dim3((nvec + per_block - 1) / per_block), dim3(kThreads), 0, ctx->stream, base, n, ncols, nvec, stride, stride_mat, results);
     WG_HIP_TRY(hipGetLastError());
@@ -285,6 +287,7 @@ int launch_fast(wg_ctx *ctx, const T *x, uint32_t n, T *result) {
     if (nparts == 0) nparts = 1; // n == 0: one workgroup writes the init value, like the reference (reduce.wgsl with an empty loop)
     void *ws = nullptr;
     if (int rc = wg_ctx_workspace(ctx, (size_t)nparts * sizeof(float), &ws)) return rc;
+    wg_path(ctx, "reduce.fast/np=%u", nparts);
     hipLaunchKernelGGL((reduce_fast_pass1<OP, T>), dim3(nparts), dim3(kThreads), 0, ctx->stream, x, n, chunk, (float *)ws);
     WG_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL((reduce_fast_pass2<OP, T>), dim3(1), dim3(kThreads), 0, ctx->stream, (const float *)ws, nparts, result);
