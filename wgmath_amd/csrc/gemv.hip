@@ -740,7 +740,10 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
     a.rows_out = rows_out; a.k = k; a.nrhs = nrhs; a.k_per_split = k_per_split;
     a.out = out;
     a.part = nullptr;
-    if (nsplit > 1) { // f32 partial sums whatever the element type
+    // launch-bound sizes: one kernel without partials beats split + combine (1024 x 1024: 12.6 -> ~9 us per eager dispatch); it needs no workspace
+    // (so that a recording on a fresh context does not ask for one)
+    const bool small = uses_small_kernel(cus, trans, rows_out, k, nrhs, nsplit);
+    if (nsplit > 1 && !small) { // f32 partial sums whatever the element type
         size_t bytes = (size_t)nmats * nsplit * nrhs * rows_out * sizeof(float);
         void *ws = nullptr;
         if (int rc = wg_ctx_workspace(ctx, bytes, &ws)) return rc;
@@ -754,9 +757,7 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
         a.dst_batch = out_batch;
     }
 
-    // launch-bound sizes: one kernel without partials beats split + combine (1024 x 1024: 12.6 -> ~9 us per eager dispatch)
-    if (uses_small_kernel(cus, trans, rows_out, k, nrhs, nsplit)) {
-        a.part = nullptr; a.ld_dst = out_ld; a.dst_split = 0; a.dst_batch = out_batch;
+    if (small) {
         const int rl = gemv_small_rl(rows_out);
         wg_path(ctx, "gemv.small/rl=%d", rl);
         const dim3 sg(ceil_div(rows_out, 4u * (uint32_t)rl), nrhs, nmats);
