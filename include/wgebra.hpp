@@ -10,6 +10,7 @@
 
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -48,6 +49,25 @@ template <> struct dtype_of<float> { static constexpr wg_dtype value = WG_F32; }
 #if defined(__FLT16_MANT_DIG__)
 template <> struct dtype_of<_Float16> { static constexpr wg_dtype value = WG_F16; };
 #endif
+// bfloat16 (WG_BF16, extension): the 16 bits, with the two host conversions of the contract (wgebra_hip.h wg_dtype) -- from_float is ONE round-to-nearest-even (a NaN stays
+// a quiet NaN, a finite value past the largest bf16 becomes Inf, subnormals are kept), to_float is exact.
+struct bf16 {
+    uint16_t bits;
+    static bf16 from_float(float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        if ((u & 0x7FFFFFFFu) > 0x7F800000u) return bf16{ (uint16_t)((u >> 16) | 0x0040u) };
+        return bf16{ (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16) };
+    }
+    float to_float() const {
+        const uint32_t u = (uint32_t)bits << 16;
+        float f;
+        std::memcpy(&f, &u, 4);
+        return f;
+    }
+};
+static_assert(sizeof(bf16) == 2, "bf16 is the 16 bits");
+template <> struct dtype_of<bf16> { static constexpr wg_dtype value = WG_BF16; };
 
 // Everything that owns a handle created on a context (tensors, command buffers) shares ownership of that context: wg_buf_destroy /
 // wg_cmdbuf_destroy dereference it, so it must be destroyed last -- like wgpu buffers keep their wgpu::Device alive.
@@ -462,3 +482,8 @@ struct CopyView {
 };
 
 } // namespace wgebra
+
+// Short name: wg::bf16, wg::Gemm, ... A program that has a `wg` of its own defines WGEBRA_NO_WG_ALIAS before including this header.
+#ifndef WGEBRA_NO_WG_ALIAS
+namespace wg = wgebra;
+#endif

@@ -36,7 +36,8 @@ extern "C" {
 #endif
 
 #define WGEBRA_HIP_ABI_VERSION 5 /* 5: wg_debug_take_path; and the round-6 additions that came without a bump: wg_copy_view, wg_timestamps_reserve,
-                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE;
+                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE; and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
+                                    that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
 
@@ -59,7 +60,20 @@ typedef enum wg_status {
 /* ------------------------------------------------------------------------------------------------ */
 /* enums: same names and ORDER as the Rust enums                                                     */
 /* ------------------------------------------------------------------------------------------------ */
-typedef enum wg_dtype { WG_F32 = 0, WG_F16 = 1 } wg_dtype; /* reference kernels are f32 only; F16 is this build's extension */
+/* reference kernels are f32 only; F16 and BF16 are this build's extensions. WG_BF16 (bfloat16: 8 exponent bits, 8 significant bits) is accepted by every entry
+ * point that takes WG_F16, for the same views, shapes, variants, alpha / beta and tuning values, with the same status codes and messages. Its contract:
+ *   - bf16 -> f32 is exact (the 16 bits become the high half of the f32); f32 -> bf16 is ONE round-to-nearest-even at the store: NaN stays a quiet NaN,
+ *     +-Inf stays +-Inf, a finite f32 past the largest bf16 (~3.39e38) becomes Inf, subnormals are flushed neither when read nor when written;
+ *   - Gemm / Gemv: products of bf16 operands are exact in f32, accumulation is f32 in the same orders as the f16 kernels (v_mfma_f32_16x16x32_bf16), the epilogue
+ *     forms alpha*acc + beta*c in f32 and rounds once; beta == 0 never reads `out`; (1, 0) is bit-identical to wg_gemm;
+ *   - Reduce family: elements are widened, folded in f32 in the reference order (the fixed chunked order for wg_reduce_fast), the result is rounded once;
+ *     an empty vector gives the op's initial value rounded to bf16;
+ *   - OpAssign / Axpy: computed in f32 on the widened elements, rounded once;
+ *   - wg_copy_view / wg_cube_to_matrix / wg_all_gather (ncclBfloat16) move the 16 bits unchanged;
+ *   - wg_gemm_sharded / wg_gemm_sharded_panels take it panel by panel (the one-launch forms are f16 only; bf16 silently takes the panel launches, as f32 does);
+ *   - wg_debug_take_path: the f16 tags with the element prefix "f16." replaced by "bf16." ("bf16.cont", "bf16.pad/c=seed>bf16.t128/ns=1"); the dtype-free tags
+ *     ("gemv.n/...", "reduce.rows4/...", "splitk.reduce/...") are the same for every element type. */
+typedef enum wg_dtype { WG_F32 = 0, WG_F16 = 1, WG_BF16 = 2 } wg_dtype;
 
 typedef enum wg_gemm_variant { /* wgebra gemm.rs:26-35 */
     WG_GEMM = 0, WG_GEMM_FAST = 1, WG_GEMM_TR = 2, WG_GEMM_TR_FAST = 3
@@ -186,6 +200,8 @@ int wg_debug_take_path(wg_ctx *ctx, char *buf, size_t cap);
  * kernel families by shape; a knob forces one choice for every later call on this context. Defaults come from the environment
  * ONCE, when the context is created (WG_F16_TILE, WG_F16_SCHED, WG_F32_SKINNY, WG_F32_PANELS, WG_F16_BALANCE): the dispatch path itself never
  * reads the environment.
+ * The WG_TUNE_F16_* knobs mean "the 16-bit Gemm family": the bf16 kernels are the f16 sources compiled for the other element type, share the launcher's dispatch
+ * tree and are steered by the same knobs in the same way.
  */
 typedef enum wg_tuning {
     WG_TUNE_F16_TILE = 0,    /* 0 = by shape (default), 128 / 256 = force the 128 x 128 / 256 x 256 f16 kernel family, 256128 = the 256 x 128 tile (two
@@ -267,7 +283,7 @@ int wg_buf_fill_zero(wg_ctx *ctx, wg_buf *buf);
  *                   sides, without any copy. Only a view that exceeds its buffer is an error.
  *   *_FAST        : the reference requires K % 256 == 0 and reads out of bounds otherwise (gemm.wgsl:40,162);
  *                   here every K % 4 == 0 is accepted and all four variants run the same tuned kernel.
- * dtype WG_F16 (extension): f16 operands, f32 accumulation, result rounded once (RNE) to f16.
+ * dtype WG_F16 (extension): f16 operands, f32 accumulation, result rounded once (RNE) to f16. WG_BF16 (extension): likewise on bfloat16 operands (wg_dtype).
  */
 int wg_gemm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype,
             wg_buf *out, wg_view_shape out_shape,
@@ -277,7 +293,7 @@ int wg_gemm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype,
 /*
  * Extension: BLAS-style update  out = alpha * op(m1) * m2 + beta * out.  Same views, checks and variants as
  * wg_gemm; beta == 0 never reads `out` (NaN/Inf there are overwritten, like wg_gemm), and (alpha, beta) = (1, 0) is
- * bit-identical to wg_gemm. alpha, beta are f32 for both dtypes; f16: alpha*acc + beta*c is formed in f32 and rounded once.
+ * bit-identical to wg_gemm. alpha, beta are f32 for every dtype; f16 and bf16: alpha*acc + beta*c is formed in f32 and rounded once.
  */
 int wg_gemm_ex(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, float alpha, float beta,
                wg_buf *out, wg_view_shape out_shape,
@@ -292,7 +308,7 @@ int wg_gemm_ex(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, float alpha
  *                   vec4-aligned run on the matrix where it lies, one pass over it per right-hand side (gemv_any.hip: 16-byte loads at
  *                   element-aligned addresses).
  *   WG_GEMV_TR_FAST with m rows % 128 != 0 silently runs as WG_GEMV_TR (gemv.rs:99-104) -- same kernel here.
- * dtype WG_F16 (extension): f16 elements, f32 accumulation, one rounding at the store -- the same HBM-bound kernels.
+ * dtype WG_F16 (extension): f16 elements, f32 accumulation, one rounding at the store -- the same HBM-bound kernels. WG_BF16 (extension): likewise on bfloat16 elements.
  * Several right-hand sides: one pass over the matrix for all of them; from 9 on -- and from 3 on when the matrix is past the launch-bound
  * sizes -- that pass runs on the Gemm kernels (same contract: f32 accumulation, results within the Gemv tolerance, deterministic).
  */
@@ -326,7 +342,7 @@ int wg_gemv_rm(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype,
  * then the 64..1 tree; reduce.wgsl:68-87), so Min/Max/Sum/Prod are bit-identical to it; n == 0 gives the init
  * value (0, 1, +3.4e38, -3.4e38).
  * dtype WG_F16 (extension): `value` and `result` are f16; elements are converted to f32 (exact), folded in the same order in f32,
- * and the result is rounded once (RNE) to f16. (wg_reduce_batched and wg_reduce_fast likewise.)
+ * and the result is rounded once (RNE) to f16. (wg_reduce_batched and wg_reduce_fast likewise.) WG_BF16 (extension): likewise on bfloat16 (widening is exact).
  */
 int wg_reduce(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype,
               const wg_buf *value, wg_view_shape value_shape, wg_buf *result);
@@ -368,7 +384,7 @@ int wg_op_assign(wg_ctx *ctx, wg_op_assign_variant op, wg_dtype dtype,
 /*
  * Extension (the north-star's "Axpy" -- the reference has no such operator, only OpAssign):
  * y[i] = fma(alpha, x[i], y[i]), i < y.size[0], one rounding per element. alpha = +1 / -1 reproduce WG_OP_ADD / WG_OP_SUB
- * (as `y += x` / `y -= x`) bit for bit. Same indexing, errors and skips as wg_op_assign. f16: computed in f32, rounded once.
+ * (as `y += x` / `y -= x`) bit for bit. Same indexing, errors and skips as wg_op_assign. f16 and bf16: computed in f32, rounded once.
  */
 int wg_axpy(wg_ctx *ctx, float alpha, wg_dtype dtype, wg_buf *y, wg_view_shape y_shape, const wg_buf *x, wg_view_shape x_shape);
 

@@ -32,7 +32,7 @@ int check_bounds(const char *op, const char *name, const View &v, const wg_buf *
 inline bool vec4_ok(const View &v) { return !(v.rows % 4 || v.offset % 4 || (v.cols > 1 && v.stride % 4) || (v.mats > 1 && v.stride_mat % 4)); }
 int check_common(const char *op, const wg_ctx *ctx, wg_dtype dtype, const wg_buf *const *bufs, int n) {
     if (!ctx) return wg_set_error(WG_ERR_INVALID_ARG, "%s: ctx is NULL", op);
-    if (dtype != WG_F32 && dtype != WG_F16) return wg_set_error(WG_ERR_INVALID_ARG, "%s: unknown dtype %d", op, (int)dtype);
+    if (dtype != WG_F32 && dtype != WG_F16 && dtype != WG_BF16) return wg_set_error(WG_ERR_INVALID_ARG, "%s: unknown dtype %d", op, (int)dtype);
     for (int i = 0; i < n; ++i) {
         if (!bufs[i]) return wg_set_error(WG_ERR_INVALID_ARG, "%s: buffer argument %d is NULL", op, i);
         if (bufs[i]->ctx->device != ctx->device)
@@ -53,13 +53,21 @@ inline uint32_t up8(uint32_t x) { return (x + 7u) & ~7u; }
 // accesses and LDS-DMA take element-aligned addresses); an operand that carries a LENGTH that is not a multiple of 4 is staged into a dense
 // zero-padded copy (the length rounded up to 8; zeros add nothing to a dot product), the usual kernels run, and a padded result is copied back
 // into the output view -- HBM-bound passes in a fourth context scratch (it cannot grow inside a recording).
+// the Gemm launcher of an element type (f32; the 16-bit family compiled for f16 and for bf16)
+int gemm_launch(wg_ctx *ctx, bool tr, wg_dtype dtype, uint32_t M, uint32_t N, uint32_t K, uint32_t mats, void *C, uint32_t ldc, uint64_t c_batch, wgk_mat A, wgk_mat B,
+                float alpha, float beta) {
+    if (dtype == WG_F32) return wgk_gemm_f32(ctx, tr, M, N, K, mats, (float *)C, ldc, c_batch, A, B, alpha, beta);
+    if (dtype == WG_BF16) return wgk_gemm_bf16(ctx, tr, M, N, K, mats, (wg_bf16 *)C, ldc, c_batch, A, B, alpha, beta);
+    return wgk_gemm_f16(ctx, tr, M, N, K, mats, (__half *)C, ldc, c_batch, A, B, alpha, beta);
+}
+
 int gemm_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, float alpha, float beta, wg_buf *out, const View &o, const wg_buf *m1, const View &a, const wg_buf *m2,
                 const View &b, uint32_t M, uint32_t N, uint32_t K) {
     const size_t es = wg_dtype_size(dtype);
     // Only the operands that need it are copied (round 6: a 16384 x 16384 matrix times ONE column -- N % 4 != 0, nothing else -- paid 800 us for the copy
     // of the matrix, 177 us now): a dimension that is not a multiple of 4 is rounded up to 8 in the two operands that carry it, an operand
     // whose own view is not vec4-aligned is copied at the (possibly padded) sizes, the others are used where they lie.
-    const uint32_t Mp = M % 4 ? up8(M) : M, Np = N % 4 && !(dtype == WG_F16 || M > 128u) ? up8(N) : N, Kp = K % 4 ? up8(K) : K, mats = o.mats; // (f16: any N as it is)
+    const uint32_t Mp = M % 4 ? up8(M) : M, Np = N % 4 && !(dtype != WG_F32 || M > 128u) ? up8(N) : N, Kp = K % 4 ? up8(K) : K, mats = o.mats; // (f16 / bf16: any N as it is)
     // (the kernels take any offset / leading dimension / batch stride -- element-aligned LDS-DMA and 16-byte accesses --: only lengths are padded)
     const bool sa = Mp != M || Kp != K, sb = Kp != K || Np != N, sc = Mp != M || Np != N;
     const uint64_t ae = sa ? (uint64_t)Mp * Kp : 0, be = sb ? (uint64_t)Kp * Np : 0, ce = sc ? (uint64_t)Mp * Np : 0;
@@ -87,9 +95,7 @@ int gemm_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, float alpha, float beta, w
             if (int rc = wgk_stage_copy(ctx, dtype, cp, Mp, ce, Mp, Np, C, o.stride, o.stride_mat, M, N, mats)) return rc;
         C = cp; ldc = Mp; c_batch = ce;
     }
-    if (int rc = dtype == WG_F32 ? wgk_gemm_f32(ctx, tr, Mp, Np, Kp, mats, (float *)C, ldc, c_batch, A, B, alpha, beta)
-                                 : wgk_gemm_f16(ctx, tr, Mp, Np, Kp, mats, (__half *)C, ldc, c_batch, A, B, alpha, beta))
-        return rc;
+    if (int rc = gemm_launch(ctx, tr, dtype, Mp, Np, Kp, mats, C, ldc, c_batch, A, B, alpha, beta)) return rc;
     if (!sc) return WG_OK;
     return wgk_stage_copy(ctx, dtype, (void *)elem_ptr(out, o.offset, dtype), o.stride, o.stride_mat, M, N, cp, Mp, ce, Mp, Np, mats);
 }
@@ -187,14 +193,13 @@ int wg_gemm_ex(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, float alpha
     // (f16: the kernels take any number of columns -- they clamp their loads of m2 per column and skip the stores past N --, so N is as free as the offsets;
     //  f32: likewise from 129 rows on; the few-row forms of its launcher compute the transposed product and need N % 4 == 0 --
     //  tests/test_gpu_parity.py::test_gemm_f32_any_number_of_columns fails on them without the copies)
-    const bool n_free = dtype == WG_F16 || m_rows > 128u; // (f32 with up to 128 rows: the few-row forms compute the transposed product, where N is the length that must be a multiple of 4)
+    const bool n_free = dtype != WG_F32 || m_rows > 128u; // (f32 with up to 128 rows: the few-row forms compute the transposed product, where N is the length that must be a multiple of 4)
     if ((o.cols % 4 && !n_free) || m_cols % 4 || m_rows % 4)
         return gemm_staged(ctx, tr, dtype, alpha, beta, out, o, m1, a, m2, b, m_rows, o.cols, m_cols);
     wgk_mat A = { elem_ptr(m1, a.offset, dtype), a.stride, a.stride_mat };
     wgk_mat B = { elem_ptr(m2, b.offset, dtype), b.stride, b.stride_mat };
     void *C = (void *)elem_ptr(out, o.offset, dtype);
-    if (dtype == WG_F32) return wgk_gemm_f32(ctx, tr, m_rows, o.cols, m_cols, o.mats, (float *)C, o.stride, o.stride_mat, A, B, alpha, beta);
-    return wgk_gemm_f16(ctx, tr, m_rows, o.cols, m_cols, o.mats, (__half *)C, o.stride, o.stride_mat, A, B, alpha, beta);
+    return gemm_launch(ctx, tr, dtype, m_rows, o.cols, m_cols, o.mats, C, o.stride, o.stride_mat, A, B, alpha, beta);
 }
 
 int wg_gemv(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype, wg_buf *out, wg_view_shape out_shape, const wg_buf *m,
@@ -406,7 +411,7 @@ int wg_gemm_rm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, wg_buf *out
     if (out->bytes == 0 || m1->bytes == 0 || m2->bytes == 0 || o.rows == 0 || o.cols == 0 || o.mats == 0) return WG_OK;
     const View a_cm = mk(relabel(m1_shape)); // M x K column-major
     if (int rc = check_bounds("Gemm", "m1", a_cm, m1, dtype)) return rc;
-    const size_t es = dtype == WG_F32 ? 4 : 2;
+    const size_t es = wg_dtype_size(dtype);
     const uint32_t K = a.rows, M = a.cols;
     WG_HIP_TRY(hipSetDevice(ctx->device));
     // From about a round of tiles on: the kernels that take m1 where it lies (gemm_f16_nt.hip; gemm_f32.hip's B_NC tile bodies) -- out^T (N x M) = m2^T (N x K,
@@ -414,20 +419,21 @@ int wg_gemm_rm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, wg_buf *out
     // two ways), 1 the kernels at any size.
     if (ctx->tuning[WG_TUNE_RM_TR_NATIVE] != 0) {
         const View o_cm = mk(relabel(out_shape)), b_cm = mk(relabel(m2_shape)); // N x M and N x K column-major
-        const uint32_t tile_n = dtype == WG_F16 ? 256u : 128u;                   // 256 x 256 (f16) / 256 x 128 (f32) tiles
+        const uint32_t tile_n = dtype != WG_F32 ? 256u : 128u;                   // 256 x 256 (f16, bf16) / 256 x 128 (f32) tiles
         const uint64_t tiles = (uint64_t)((o_cm.rows + 255u) / 256u) * ((o_cm.cols + tile_n - 1u) / tile_n) * o_cm.mats;
         const uint64_t cus = (uint64_t)(ctx->compute_units > 0 ? ctx->compute_units : 256);
         // (f32: the copy path's launcher cuts K / takes small tiles below a round of big tiles, which this launch does not: only from a full round on.
         //  f16: the native launcher has the mid-size tiles too (gemm_f16_t128.hip's B_NC instances): from half a round of 128 x 128 tiles on -- below that the copy
         //  path's launcher would cut K over the idle CUs, which the native kernels do not)
         const uint64_t tiles128 = (uint64_t)((o_cm.rows + 127u) / 128u) * ((o_cm.cols + 127u) / 128u) * o_cm.mats;
-        if (ctx->tuning[WG_TUNE_RM_TR_NATIVE] == 1 || (dtype == WG_F16 ? 2u * tiles128 >= cus : tiles >= cus)) {
+        if (ctx->tuning[WG_TUNE_RM_TR_NATIVE] == 1 || (dtype != WG_F32 ? 2u * tiles128 >= cus : tiles >= cus)) {
             if (int rc = check_bounds("Gemm", "m2", b_cm, m2, dtype)) return rc;
             if (int rc = check_bounds("Gemm", "out", o_cm, out, dtype)) return rc;
             const wgk_mat A = { elem_ptr(m2, b_cm.offset, dtype), b_cm.stride, b_cm.stride_mat }, B = { elem_ptr(m1, a_cm.offset, dtype), a_cm.stride, a_cm.stride_mat };
             void *o = (void *)elem_ptr(out, o_cm.offset, dtype);
-            const int rc = dtype == WG_F16 ? wgk_gemm_f16_nt(ctx, o_cm.rows, o_cm.cols, K, o_cm.mats, (__half *)o, o_cm.stride, o_cm.stride_mat, A, B)
-                                           : wgk_gemm_f32_nt(ctx, o_cm.rows, o_cm.cols, K, o_cm.mats, (float *)o, o_cm.stride, o_cm.stride_mat, A, B);
+            const int rc = dtype == WG_F16    ? wgk_gemm_f16_nt(ctx, o_cm.rows, o_cm.cols, K, o_cm.mats, (__half *)o, o_cm.stride, o_cm.stride_mat, A, B)
+                           : dtype == WG_BF16 ? wgk_gemm_bf16_nt(ctx, o_cm.rows, o_cm.cols, K, o_cm.mats, (wg_bf16 *)o, o_cm.stride, o_cm.stride_mat, A, B)
+                                              : wgk_gemm_f32_nt(ctx, o_cm.rows, o_cm.cols, K, o_cm.mats, (float *)o, o_cm.stride, o_cm.stride_mat, A, B);
             if (rc != WG_ERR_UNSUPPORTED) return rc;
         }
     }

@@ -438,7 +438,7 @@ int wg_comm_set_pipelined(wg_comm *c, int on) {
 // wait for it (wg_comm_join does), so later Gemms overlap it.
 int wg_all_gather(wg_comm *c, wg_dtype dtype, wg_buf *buf, uint64_t first_elem, uint64_t elems_per_rank) {
     if (!c || !buf) return wg_set_error(WG_ERR_INVALID_ARG, "wg_all_gather: NULL argument");
-    if (dtype != WG_F32 && dtype != WG_F16) return wg_set_error(WG_ERR_INVALID_ARG, "wg_all_gather: unknown dtype %d", (int)dtype);
+    if (dtype != WG_F32 && dtype != WG_F16 && dtype != WG_BF16) return wg_set_error(WG_ERR_INVALID_ARG, "wg_all_gather: unknown dtype %d", (int)dtype);
     if (!c->nccl) return wg_set_error(WG_ERR_UNSUPPORTED, "wg_all_gather: this communicator was created without a collective library (id == NULL)");
     if (c->ctx->recording) return wg_set_error(WG_ERR_INVALID_ARG, "wg_all_gather: collectives cannot be recorded");
     const size_t es = wg_dtype_size(dtype);
@@ -451,7 +451,7 @@ int wg_all_gather(wg_comm *c, wg_dtype dtype, wg_buf *buf, uint64_t first_elem, 
     WG_HIP_TRY(hipEventRecord(c->ev_ctx, c->ctx->stream));
     WG_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_ctx, 0));
     char *base = (char *)buf->ptr + first_elem * es;
-    ncclResult_t r = rccl().AllGather(base + (size_t)c->rank * elems_per_rank * es, base, elems_per_rank, dtype == WG_F16 ? ncclFloat16 : ncclFloat32, c->nccl, c->stream);
+    ncclResult_t r = rccl().AllGather(base + (size_t)c->rank * elems_per_rank * es, base, elems_per_rank, dtype == WG_F16 ? ncclFloat16 : dtype == WG_BF16 ? ncclBfloat16 : ncclFloat32, c->nccl, c->stream);
     if (r != ncclSuccess) return nccl_fail("ncclAllGather", r);
     c->bytes_sent += elems_per_rank * es;
     return WG_OK;
@@ -607,7 +607,7 @@ int wg_comm_set_peer_stages(wg_comm *c, wg_buf *const *peer_stage, wg_buf *const
 // ---------------------------------------------------------------------------------------------------------------
 int wg_cube_to_matrix(wg_ctx *ctx, wg_dtype dtype, const wg_buf *cube, wg_view_shape cube_shape, wg_buf *out, wg_view_shape out_shape) {
     if (!ctx || !cube || !out) return wg_set_error(WG_ERR_INVALID_ARG, "cube_to_matrix: NULL argument");
-    if (dtype != WG_F32 && dtype != WG_F16) return wg_set_error(WG_ERR_INVALID_ARG, "cube_to_matrix: unknown dtype %d", (int)dtype);
+    if (dtype != WG_F32 && dtype != WG_F16 && dtype != WG_BF16) return wg_set_error(WG_ERR_INVALID_ARG, "cube_to_matrix: unknown dtype %d", (int)dtype);
     const uint32_t mg = cube_shape.size[0], np = cube_shape.size[1], P = cube_shape.size[2];
     if (out_shape.size[0] != mg * P || out_shape.size[1] != np || out_shape.size[2] != 1)
         return wg_set_error(WG_ERR_DIM_MISMATCH, "cube_to_matrix: dimension mismatch. (cube [%u,%u,%u] -> out [%u,%u,%u])", mg, np, P, out_shape.size[0],
@@ -633,7 +633,7 @@ int wg_cube_to_matrix(wg_ctx *ctx, wg_dtype dtype, const wg_buf *cube, wg_view_s
 static int gemm_sharded_impl(wg_comm *c, wg_gemm_variant variant, wg_dtype dtype, wg_gather_mode mode, const uint32_t *widths, uint32_t nwidths, wg_buf *out,
                              wg_view_shape out_shape, const wg_buf *a_rows, wg_view_shape a_shape, const wg_buf *b, wg_view_shape b_shape) {
     if (!c || !out || !a_rows || !b) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm (sharded): NULL argument");
-    if (dtype != WG_F32 && dtype != WG_F16) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm (sharded): unknown dtype %d", (int)dtype);
+    if (dtype != WG_F32 && dtype != WG_F16 && dtype != WG_BF16) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm (sharded): unknown dtype %d", (int)dtype);
     if ((int)variant < 0 || (int)variant > 3) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: unknown variant %d", (int)variant);
     if ((int)mode < 0 || (int)mode > 3 || (int)mode == 1) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm (sharded): unknown gather mode %d", (int)mode);
     wg_ctx *ctx = c->ctx;
@@ -967,7 +967,7 @@ static int gemm_sharded_impl(wg_comm *c, wg_gemm_variant variant, wg_dtype dtype
             WG_HIP_TRY(hipEventRecord(c->ev_ctx, ctx->stream));
             WG_HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_ctx, 0));
             char *base = (char *)c->stage + slot0 * es;
-            ncclResult_t r = rccl().AllGather(base + (size_t)g * mg * np * es, base, (size_t)mg * np, dtype == WG_F16 ? ncclFloat16 : ncclFloat32, c->nccl, c->stream);
+            ncclResult_t r = rccl().AllGather(base + (size_t)g * mg * np * es, base, (size_t)mg * np, dtype == WG_F16 ? ncclFloat16 : dtype == WG_BF16 ? ncclBfloat16 : ncclFloat32, c->nccl, c->stream);
             if (r != ncclSuccess) return nccl_fail("ncclAllGather", r);
             c->bytes_sent += (uint64_t)mg * np * es;
             WG_HIP_TRY(hipEventRecord(c->ev_panel[p], c->stream));

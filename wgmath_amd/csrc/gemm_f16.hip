@@ -6,7 +6,7 @@
 // Bound: MFMA (2.5 PFLOP/s dense peak); in practice the 1400 W package power cap (profiles/r01_evidence.md).
 #include "gemm_f16_common.hpp"
 
-namespace wgf16 {
+namespace WG16_NS {
 namespace {
 
 // ===============================================================================================================
@@ -201,9 +201,9 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
         if (unit_mode == 2) { k_begin = 0; K_loc = g.K; } // a suffix unit without its prefix: the whole tile
         rem = K_loc & 63u; K_loc -= rem; rem_k0 = k_begin + K_loc;
     }
-    const _Float16 *A = g.a + z * g.a_batch + (TRANS_A ? (uint64_t)k_begin : (uint64_t)k_begin * g.lda);
-    const _Float16 *B = g.b + z * g.b_batch + k_begin;
-    _Float16 *C = g.c + z * g.c_batch;
+    const wg16_elem_t *A = g.a + z * g.a_batch + (TRANS_A ? (uint64_t)k_begin : (uint64_t)k_begin * g.lda);
+    const wg16_elem_t *B = g.b + z * g.b_batch + k_begin;
+    wg16_elem_t *C = g.c + z * g.c_batch;
     const bool paneled = g.panel.cols != 0; // workgroup-uniform
     if (paneled) { // the epilogue indexes columns globally: C + col * ldc; panel p's columns start at its own base: the cube's columns are col_stride
         // apart, this rank's slot of panel p starts slot_rows * np(p) elements into it (C already points slot_rows * cols into panel 0)
@@ -226,7 +226,7 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
     // ---- DMA addressing; ragged tiles: rows past the end are clamped to the last valid one (results discarded by the epilogue) ----
     // A half-stage = 16 pieces of 1 KiB, wave stages P = 4 wave + q; B full stage = 32 pieces, wave stages P = 8 wave + q.
     uint32_t a_voff[TRANS_A ? 8 : 4], b_voff[8];
-    const _Float16 *a_base, *b_base = B + (uint64_t)n0 * g.ldb;
+    const wg16_elem_t *a_base, *b_base = B + (uint64_t)n0 * g.ldb;
     if constexpr (TRANS_A) a_base = A + (uint64_t)m0 * g.lda; else a_base = A + m0;
     // K remainder (see the prologue): where its k-values start, and the loop's stage 0 becomes the remainder -- every base one stage back
     const uint32_t rem_dk = rem_k0 - k_begin;
@@ -268,12 +268,12 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
     // NN: + slot * 16 KiB + q * 1 KiB (4 half-stage slots); TN: + slot * 32 KiB + q * 1 KiB (2 full-stage slots)
     const uint32_t lds_a_wave = __builtin_amdgcn_readfirstlane(lds_base + wave * (TRANS_A ? 8192 : 4096));
     const uint32_t lds_b_wave = __builtin_amdgcn_readfirstlane(lds_base + M16_B_BASE + wave * 8192); // + slot * 32 KiB + q * 1 KiB
-    auto a_src = [&](uint32_t H) -> const _Float16 * { // NN: global base of half-stage H;  TN: of full stage H
+    auto a_src = [&](uint32_t H) -> const wg16_elem_t * { // NN: global base of half-stage H;  TN: of full stage H
         const char *p0;
         if constexpr (TRANS_A) p0 = (const char *)(a_base + H * 64u); else p0 = (const char *)(a_base + (uint64_t)(H * BKH) * g.lda);
-        return (const _Float16 *)(p0 - M16_BIAS);
+        return (const wg16_elem_t *)(p0 - M16_BIAS);
     };
-    auto b_src = [&](uint32_t stage) -> const _Float16 * { return (const _Float16 *)((const char *)(b_base + 64u * stage) - M16_BIAS); };
+    auto b_src = [&](uint32_t stage) -> const wg16_elem_t * { return (const wg16_elem_t *)((const char *)(b_base + 64u * stage) - M16_BIAS); };
 
     // ---- per-lane LDS read addresses (bytes from the start of the LDS) for half-step parity 0 / 1 of a stage ----
     uint32_t vbaseA[2], vbaseB[2];
@@ -471,7 +471,7 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
         static_for<64>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int t = j >> 3, u = j & 7;
-            acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, a_r[HS][t]), b_f[HS][u], acc[t][u], 0, 0, 0);
+            acc[t][u] = WG16_MFMA(__builtin_bit_cast(half8_t, a_r[HS][t]), b_f[HS][u], acc[t][u], 0, 0, 0);
             if constexpr (decltype(has_next)::value) frag_slot(jc, HS ^ 1);
             if constexpr (ADMA && j == DO - 1) m16_set_m0(lds_a_wave + rD);
             if constexpr (BDMA && j == DO + 4 * DS - 4) { lb = lds_b_wave + oD + (HS == 0 ? 4096u : 0u); asm volatile("" : "+s"(lb)); }
@@ -526,7 +526,7 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
         static_for<64>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int t = j >> 3, u = j & 7;
-            acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, a_r[HS][t]), b_f[HS][u], acc[t][u], 0, 0, 0);
+            acc[t][u] = WG16_MFMA(__builtin_bit_cast(half8_t, a_r[HS][t]), b_f[HS][u], acc[t][u], 0, 0, 0);
             if constexpr (decltype(has_next)::value) frag_slot(jc, HS ^ 1);
             // M0 values: computed one slot before the write that uses them
             if constexpr (ADMA && j == DO - 2) { la = lds_a_wave + oAD; asm volatile("" : "+s"(la)); }
@@ -778,7 +778,7 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
 #define WG_EPI_STORE -1 // -1: by GemmArgs::c_stream (shipped); experiments: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1, 4 sc1 nt for every launch
 #endif
     // (u, p) in the lane's own layout: rows row0 + 32 p .. + 7 of column n0 + 128 wn + 16 u + i16, alpha / beta applied, rounded once
-    auto pack = [&](int u, int p, bool ok, const _Float16 *cc) -> half8_t {
+    auto pack = [&](int u, int p, bool ok, const wg16_elem_t *cc) -> half8_t {
         float r[8];
 #pragma unroll
         for (int q = 0; q < 4; ++q) { // (odd lane rows of the swap-free Gemm: the pair's tiles in exchanged order)
@@ -796,13 +796,13 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
         }
         half8_t v;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = (_Float16)r[q];
+        for (int q = 0; q < 8; ++q) v[q] = (wg16_elem_t)r[q];
         return v;
     };
     // (every hand-written store carries its own `s_nop 1`: a store of more than 64 bits reads its data registers AFTER it issues, the compiler's hazard
     // recognizer does not look inside an asm statement, and a read-out of the next pack into the same registers right behind the store changed the first
     // dword for lanes 12 .. 15 of every row -- seen in the continuous kernel, round 5)
-    auto store8 = [&](_Float16 *dst, half8_t v) {
+    auto store8 = [&](wg16_elem_t *dst, half8_t v) {
         if (paneled) { // write-through to memory: when the store is acknowledged a copy engine may read it
             if constexpr (WG_PANEL_STORE == 0) *reinterpret_cast<half8_u *>(dst) = v; // (timing experiments only: NOT visible to a copy engine in time)
             else if constexpr (WG_PANEL_STORE == 1) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
@@ -826,7 +826,7 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
     for (int u = 0; u < 8; ++u) {
         const uint32_t col = n0 + 128u * wn + 16u * u + i16;
         if (!full_tile && col >= g.N) continue;
-        _Float16 *cc = C + (uint64_t)col * ldc + row0;
+        wg16_elem_t *cc = C + (uint64_t)col * ldc + row0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             if (!(full_tile || row0 + 32 * p < g.M)) continue; // 8 consecutive rows, all in or all out (M % 8 == 0)
@@ -891,7 +891,7 @@ static __device__ uint32_t m16_acquire_tile(const GemmArgs &g) {
 }
 
 template <bool TRANS_A>
-__global__ __launch_bounds__(256, 1) void gemm_f16_m16_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256, 1) void WG16_SYM(gemm_, _m16_kernel)(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) char smem[160 * 1024];
     uint32_t bid = blockIdx.x;
     uint32_t mode = 0, kb = 0, ns = 0, pair = 0; // balance unit (BalancePlan); 0: a whole tile
@@ -933,10 +933,10 @@ template <int I> struct AccQuad;
 #define WG_ACC_QUAD_DEF(I, R0, R1, R2, R3)                                                                                                              \
     template <> struct AccQuad<I> {                                                                                                                     \
         static __device__ __forceinline__ void mfma(half8_t a, half8_t b) {                                                                             \
-            asm volatile("v_mfma_f32_16x16x32_f16 a[" #R0 ":" #R3 "], %0, %1, a[" #R0 ":" #R3 "]" ::"v"(a), "v"(b) : "a" #R0, "a" #R1, "a" #R2, "a" #R3);  \
+            asm volatile(WG16_MFMA_ASM " a[" #R0 ":" #R3 "], %0, %1, a[" #R0 ":" #R3 "]" ::"v"(a), "v"(b) : "a" #R0, "a" #R1, "a" #R2, "a" #R3);  \
         }                                                                                                                                               \
         static __device__ __forceinline__ void mfma0(half8_t a, half8_t b) { /* the quad's first product of a tile: C = 0 instead of a zeroing pass */      \
-            asm volatile("v_mfma_f32_16x16x32_f16 a[" #R0 ":" #R3 "], %0, %1, 0" ::"v"(a), "v"(b) : "a" #R0, "a" #R1, "a" #R2, "a" #R3);                     \
+            asm volatile(WG16_MFMA_ASM " a[" #R0 ":" #R3 "], %0, %1, 0" ::"v"(a), "v"(b) : "a" #R0, "a" #R1, "a" #R2, "a" #R3);                     \
         }                                                                                                                                               \
         static __device__ __forceinline__ void read(float &x0, float &x1, float &x2, float &x3) {                                                       \
             asm volatile("v_accvgpr_read_b32 %0, a" #R0 "\n\tv_accvgpr_read_b32 %1, a" #R1 "\n\tv_accvgpr_read_b32 %2, a" #R2 "\n\tv_accvgpr_read_b32 %3, a" #R3 \
@@ -1310,14 +1310,14 @@ __device__ __forceinline__ void m16_cont(const GemmArgs &g, char *const smem, co
         // ---- epilogue of `tile`: the stores are NOT waited for; they drain under the next tile's first stage. ONE basic block (no alpha / beta / store-flavour
         // branches: beta == 0 is the launcher's condition, x * 1.0f is x) with a scheduling fence per pack: with branches between the packs the compiler brings all
         // 256 accumulators over to VGPRs at the loop's exit, on top of the live fragments, and spills (ISA of the first cut: 22 dwords, reloaded behind the stores).
-        _Float16 *C = g.c + c_off;
+        wg16_elem_t *C = g.c + c_off;
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory"); // the last MFMA's result is out of the pipe before the first hand-written read
         const bool full_tile = m0 + BM <= g.M && n0 + BN <= g.N; // workgroup-uniform
         static_for<8>([&](auto uc) {
             constexpr int u = decltype(uc)::value;
             const uint32_t col = n0 + 128u * wn + 16u * u + col_w;
             const bool col_ok = full_tile || col < g.N;
-            _Float16 *cc = C + (uint64_t)(col_ok ? col : n0) * ldc + m0 + row_w;
+            wg16_elem_t *cc = C + (uint64_t)(col_ok ? col : n0) * ldc + m0 + row_w;
             static_for<4>([&](auto pc) {
                 constexpr int p = decltype(pc)::value;
                 const bool ok = col_ok && (full_tile || m0 + row_w + 32u * p < g.M); // 8 consecutive rows, all in or all out (M % 8 == 0)
@@ -1332,7 +1332,7 @@ __device__ __forceinline__ void m16_cont(const GemmArgs &g, char *const smem, co
                         asm volatile("" : "+v"(r[q])); // the f32 product, THEN one rounding to f16, as m16_tile's epilogue does it (in one expression the two
                                                        // become v_fma_mix*_f16, whose f16 results differ in the denormal range: 477 of 2^25 elements, alpha = -0.375)
                     }
-                    v[q] = (_Float16)r[q];
+                    v[q] = (wg16_elem_t)r[q];
                 }
                 if constexpr (!TRANS_A && WG_NN_NOSWAP) { // odd lane rows hold the pair's tiles in exchanged order (rows + 4..7 in tile 2 p): exchanged back on the PACKED
                                                           // halves -- two selects per tile instead of four (the epilogue is the tile boundary's cost: m16_cont's header)
@@ -1346,7 +1346,7 @@ __device__ __forceinline__ void m16_cont(const GemmArgs &g, char *const smem, co
                     for (int d = 0; d < 4; ++d) w[d] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)perm_src, (int)w[d]);
                     v = __builtin_bit_cast(half8_t, w);
                 }
-                _Float16 *dst = cc + 32 * p;
+                wg16_elem_t *dst = cc + 32 * p;
 #ifndef WG_CONT_ABLATE
 #define WG_CONT_ABLATE 0 // timing experiments only (results are garbage): 1 = the epilogue issues no stores; 2 = no read-out / convert either (the accumulators are simply overwritten)
 #endif
@@ -1377,7 +1377,7 @@ __device__ __forceinline__ void m16_cont(const GemmArgs &g, char *const smem, co
 // patch, 5 % slower). A boundary inside a walk saves 3-5 us, 2 % of a K = 8192 tile, on three tiles of four of three quarters of the tiles: removed.
 // profiles/r05_f16_chunked_walk_*.txt.)
 template <bool TRANS_A, bool STREAM, bool ALPHA1>
-__global__ __launch_bounds__(256, 1) void gemm_f16_m16c_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256, 1) void WG16_SYM(gemm_, _m16c_kernel)(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) char smem[160 * 1024];
     // the tiles the hardware's round-robin deal would have given this CU: blockIdx.x, + gridDim.x, ... below g.sched_tiles
     const uint32_t first = blockIdx.x;
@@ -1392,7 +1392,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f16_m16c_kernel(GemmArgs g) {
 // run on a nearly empty chip for a full tile time. The launcher then runs the full rounds normally and cuts the few tail tiles
 // along K over the idle CUs (f32 partial tiles in the workspace); this kernel adds a tile's partials in ASCENDING split order
 // (deterministic) and writes it with the usual alpha / beta / ragged-edge rules. grid = (tail tiles, 64): 4 columns per block.
-__global__ __launch_bounds__(256) void gemm_f16_tail_reduce(GemmArgs g) {
+__global__ __launch_bounds__(256) void WG16_SYM(gemm_, _tail_reduce)(GemmArgs g) {
     uint32_t tm, tn;
     tile_of(blockIdx.x + g.tile_base, g.tiles_m, g.tiles_n, tm, tn);
     const uint32_t row = tm * BM + 4u * (threadIdx.x & 63u), col = tn * BN + blockIdx.y * 4u + (threadIdx.x >> 6);
@@ -1403,15 +1403,15 @@ __global__ __launch_bounds__(256) void gemm_f16_tail_reduce(GemmArgs g) {
         const float4 q = *reinterpret_cast<const float4 *>(p + (uint64_t)i * g.tail_tiles * 65536u);
         s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
     }
-    _Float16 *o = g.c + (uint64_t)col * g.ldc + row;
-    struct alignas(2) h4 { _Float16 v[4]; }; // (C at any element-aligned address)
+    wg16_elem_t *o = g.c + (uint64_t)col * g.ldc + row;
+    struct alignas(2) h4 { wg16_elem_t v[4]; }; // (C at any element-aligned address)
     if (g.alpha != 1.f) { s.x *= g.alpha; s.y *= g.alpha; s.z *= g.alpha; s.w *= g.alpha; }
     if (g.beta != 0.f) {
         const h4 t = *reinterpret_cast<const h4 *>(o);
         s.x = fmaf(g.beta, (float)t.v[0], s.x); s.y = fmaf(g.beta, (float)t.v[1], s.y);
         s.z = fmaf(g.beta, (float)t.v[2], s.z); s.w = fmaf(g.beta, (float)t.v[3], s.w);
     }
-    const h4 r = { { (_Float16)s.x, (_Float16)s.y, (_Float16)s.z, (_Float16)s.w } };
+    const h4 r = { { (wg16_elem_t)s.x, (wg16_elem_t)s.y, (wg16_elem_t)s.z, (wg16_elem_t)s.w } };
     *reinterpret_cast<h4 *>(o) = r;
 }
 
@@ -1419,7 +1419,7 @@ __global__ __launch_bounds__(256) void gemm_f16_tail_reduce(GemmArgs g) {
 } // namespace
 } // namespace wgf16
 
-using namespace wgf16;
+using namespace WG16_NS;
 
 namespace {
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -1553,21 +1553,21 @@ uint32_t bal_plan(const double rel[8], uint32_t tiles, uint32_t S, bool forced, 
 }
 
 thread_local bool g_padding = false; // set while wgk_gemm_f16 runs on padded copies (see the staging branch)
-int pad_copy(wg_ctx *ctx, _Float16 *dst, uint32_t ld_dst, uint64_t dst_batch, uint32_t rd, uint32_t cd, const _Float16 *src, uint32_t ld_src,
+int pad_copy(wg_ctx *ctx, wg16_elem_t *dst, uint32_t ld_dst, uint64_t dst_batch, uint32_t rd, uint32_t cd, const wg16_elem_t *src, uint32_t ld_src,
              uint64_t src_batch, uint32_t rs, uint32_t cs, uint32_t nmats) {
     // zero-padded copy of a column-major block, any alignment on either side (transpose.hip: 16-byte accesses with a byte shift)
-    return wgk_stage_copy(ctx, WG_F16, dst, ld_dst, dst_batch, rd, cd, src, ld_src, src_batch, rs, cs, nmats);
+    return wgk_stage_copy(ctx, WG16_DTYPE, dst, ld_dst, dst_batch, rd, cd, src, ld_src, src_batch, rs, cs, nmats);
 }
 } // namespace
 
-int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
-                 __half *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha, float beta, const wgk_panels *panels) {
+int WG16_SYM(wgk_gemm_, )(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
+                 wg16_ext_t *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha, float beta, const wgk_panels *panels) {
     if (M == 0 || N == 0 || nmats == 0) return panels ? WG_ERR_UNSUPPORTED : WG_OK;
     if (nmats > 65535) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: more than 65535 matrices in one call");
     GemmArgs g;
-    g.a = (const _Float16 *)m1.ptr; g.lda = m1.ld; g.a_batch = m1.batch;
-    g.b = (const _Float16 *)m2.ptr; g.ldb = m2.ld; g.b_batch = m2.batch;
-    g.c = (_Float16 *)out; g.ldc = out_ld; g.c_batch = out_batch;
+    g.a = (const wg16_elem_t *)m1.ptr; g.lda = m1.ld; g.a_batch = m1.batch;
+    g.b = (const wg16_elem_t *)m2.ptr; g.ldb = m2.ld; g.b_batch = m2.batch;
+    g.c = (wg16_elem_t *)out; g.ldc = out_ld; g.c_batch = out_batch;
     g.M = M; g.N = N; g.K = K;
     g.alpha = alpha; g.beta = beta;
     {   // the result past the caches when it would push the operands out of the Infinity Cache (see GemmArgs::c_stream); beta != 0 reads C back
@@ -1592,7 +1592,7 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
     if (WG_F16_SKINNY && trans && !panels && N <= 16u && M >= 512u && M % 4u == 0 && K >= 256u && K % 8u == 0 && m1.ld % 8u == 0 && m2.ld % 8u == 0 &&
         out_ld % 4u == 0 && al16(m1.ptr) && al16(m2.ptr) && ((uintptr_t)out & 7) == 0 && (nmats == 1 || (m1.batch % 8u == 0 && m2.batch % 8u == 0 && out_batch % 4u == 0)) &&
         (uint64_t)M * K * 2u >= (16ull << 20) && (uint64_t)m1.ld * 32u * 2u < (1ull << 31) && (uint64_t)m2.ld * 32u * 2u < (1ull << 31))
-        return wgk_gemm_f16_skinny(ctx, M, N, K, nmats, out, out_ld, out_batch, m1, m2, alpha, beta);
+        return WG16_SYM(wgk_gemm_, _skinny)(ctx, M, N, K, nmats, out, out_ld, out_batch, m1, m2, alpha, beta);
     // 32-bit DMA offsets within a tile: rows * ld * 2 bytes must stay below 2^31
     const bool off_ok = (uint64_t)m1.ld * 2u * (trans ? 256u : 32u) < (1ull << 31) && (uint64_t)m2.ld * 2u * 256u < (1ull << 31);
     // (N is free: B rows are clamped per column and the epilogues skip columns >= N)
@@ -1686,7 +1686,7 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
             t.nsplit = 1; t.k_per_split = K; t.part = nullptr;
             const uint64_t tiles_t = (uint64_t)t.tiles_m * t.tiles_n;
             if (tiles_t <= 0x7fffffffull && nmats <= 65535u) {
-                wg_path(ctx, "f16.t256x128");
+                wg_path(ctx, WG16_TAG ".t256x128");
                 return t128_launch(ctx, trans, dim3((uint32_t)tiles_t, nmats), t, 256);
             }
         }
@@ -1737,9 +1737,9 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
                     t.part = (float *)ws;
                 }
                 if ((uint64_t)nmats * ns <= 65535) {
-                    wg_path(ctx, "f16.t128/ns=%u", ns);
+                    wg_path(ctx, WG16_TAG ".t128/ns=%u", ns);
                     if (int rc = t128_launch(ctx, trans, dim3((uint32_t)tiles128, nmats * ns), t)) return rc;
-                    if (ns > 1) return wg_splitk_reduce(ctx, t.part, ns, M, N, nmats, WG_F16, out, out_ld, out_batch, alpha, beta);
+                    if (ns > 1) return wg_splitk_reduce(ctx, t.part, ns, M, N, nmats, WG16_DTYPE, out, out_ld, out_batch, alpha, beta);
                     return WG_OK;
                 }
             }
@@ -1804,9 +1804,9 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
                     if (cont != 0 && applies && (cont == 1 || by_rule)) {
                         const dim3 grid((uint32_t)cus), block(256);
                         gm.sched = nullptr; gm.sched_tiles = (uint32_t)all;
-                        wg_path(ctx, "f16.cont");
+                        wg_path(ctx, WG16_TAG ".cont");
                         auto go = [&](auto tr_c, auto st_c, auto a1_c) {
-                            hipLaunchKernelGGL((gemm_f16_m16c_kernel<decltype(tr_c)::value, decltype(st_c)::value, decltype(a1_c)::value>), grid, block, 0, ctx->stream, gm);
+                            hipLaunchKernelGGL((WG16_SYM(gemm_, _m16c_kernel)<decltype(tr_c)::value, decltype(st_c)::value, decltype(a1_c)::value>), grid, block, 0, ctx->stream, gm);
                         };
                         auto by_alpha = [&](auto tr_c, auto st_c) { if (gm.alpha == 1.f) go(tr_c, st_c, std::true_type{}); else go(tr_c, st_c, std::false_type{}); };
                         auto by_stream = [&](auto tr_c) { if (gm.c_stream) by_alpha(tr_c, std::true_type{}); else by_alpha(tr_c, std::false_type{}); };
@@ -1849,9 +1849,9 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
                         } else gm.bal = BalancePlan{};
                     }
                 }
-                wg_path(ctx, "f16.m16%s/ns=%u", gm.bal.on ? "bal" : dyn ? "q" : "", gm.nsplit);
-                if (trans) hipLaunchKernelGGL((gemm_f16_m16_kernel<true>), dim3(nwg, gm.nsplit * nmats), dim3(256), 0, ctx->stream, gm);
-                else hipLaunchKernelGGL((gemm_f16_m16_kernel<false>), dim3(nwg, gm.nsplit * nmats), dim3(256), 0, ctx->stream, gm);
+                wg_path(ctx, WG16_TAG ".m16%s/ns=%u", gm.bal.on ? "bal" : dyn ? "q" : "", gm.nsplit);
+                if (trans) hipLaunchKernelGGL((WG16_SYM(gemm_, _m16_kernel)<true>), dim3(nwg, gm.nsplit * nmats), dim3(256), 0, ctx->stream, gm);
+                else hipLaunchKernelGGL((WG16_SYM(gemm_, _m16_kernel)<false>), dim3(nwg, gm.nsplit * nmats), dim3(256), 0, ctx->stream, gm);
                 return WG_OK;
             };
             // tail split: full rounds as they are, the few tiles of a nearly empty last round cut along K over the idle CUs
@@ -1879,11 +1879,11 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
                 if (int rc = launch_tiles(g, full)) return rc; // the full rounds
                 GemmArgs gt = g; // the tail tiles, cut along K
                 gt.tile_base = full; gt.tail_tiles = tail; gt.nsplit = tail_split; gt.k_per_split = tail_kps; gt.part = (float *)ws;
-                wg_path(ctx, "f16.m16tail/ns=%u", tail_split);
-                wg_path(ctx, "f16.tail_reduce");
-                if (trans) hipLaunchKernelGGL((gemm_f16_m16_kernel<true>), dim3(tail, tail_split), dim3(256), 0, ctx->stream, gt);
-                else hipLaunchKernelGGL((gemm_f16_m16_kernel<false>), dim3(tail, tail_split), dim3(256), 0, ctx->stream, gt);
-                hipLaunchKernelGGL(gemm_f16_tail_reduce, dim3(tail, 64), dim3(256), 0, ctx->stream, gt);
+                wg_path(ctx, WG16_TAG ".m16tail/ns=%u", tail_split);
+                wg_path(ctx, WG16_TAG ".tail_reduce");
+                if (trans) hipLaunchKernelGGL((WG16_SYM(gemm_, _m16_kernel)<true>), dim3(tail, tail_split), dim3(256), 0, ctx->stream, gt);
+                else hipLaunchKernelGGL((WG16_SYM(gemm_, _m16_kernel)<false>), dim3(tail, tail_split), dim3(256), 0, ctx->stream, gt);
+                hipLaunchKernelGGL(WG16_SYM(gemm_, _tail_reduce), dim3(tail, 64), dim3(256), 0, ctx->stream, gt);
                 WG_HIP_TRY(hipGetLastError());
                 return WG_OK;
             }
@@ -1900,7 +1900,7 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
 #endif
         }
         WG_HIP_TRY(hipGetLastError());
-        if (nsplit > 1) return wg_splitk_reduce(ctx, g.part, nsplit, M, N, nmats, WG_F16, out, out_ld, out_batch, alpha, beta);
+        if (nsplit > 1) return wg_splitk_reduce(ctx, g.part, nsplit, M, N, nmats, WG16_DTYPE, out, out_ld, out_batch, alpha, beta);
         return WG_OK;
     } else if (!g_padding && (uint64_t)M * N * K >= (1ull << 24) && K > 0 && nmats <= 65535u) {
         struct Guard { Guard() { g_padding = true; } ~Guard() { g_padding = false; } } guard; // the padded call must not pad again
@@ -1919,36 +1919,37 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
         // every region starts 16-byte aligned: element counts rounded up to 8
         const uint64_t a_sz = ((a_elems + 7u) & ~7ull), b_sz = ((b_elems + 7u) & ~7ull), c_sz = ((c_elems + 7u) & ~7ull);
         void *ws = nullptr;
-        if (int rc = wg_ctx_pad_workspace(ctx, (size_t)((a_sz + b_sz + c_sz) * nmats * sizeof(_Float16)) + 16, &ws)) return rc;
-        _Float16 *ap = (_Float16 *)ws, *bp = ap + a_sz * nmats, *cp = bp + b_sz * nmats;
-        wg_path(ctx, "f16.pad%s>", c_ok ? "" : beta != 0.f ? "/c=seed" : "/c");
+        if (int rc = wg_ctx_pad_workspace(ctx, (size_t)((a_sz + b_sz + c_sz) * nmats * sizeof(wg16_elem_t)) + 16, &ws)) return rc;
+        wg16_elem_t *ap = (wg16_elem_t *)ws, *bp = ap + a_sz * nmats, *cp = bp + b_sz * nmats;
+        wg_path(ctx, WG16_TAG ".pad%s>", c_ok ? "" : beta != 0.f ? "/c=seed" : "/c");
         wgk_mat a2 = m1, b2 = m2;
         if (!a_ok) { // op(A) is M x K: stored M x K or, transposed, K x M
-            if (trans) { if (int rc = pad_copy(ctx, ap, Kp, a_sz, Kp, Mp, (const _Float16 *)m1.ptr, m1.ld, m1.batch, K, M, nmats)) return rc; }
-            else { if (int rc = pad_copy(ctx, ap, Mp, a_sz, Mp, Kp, (const _Float16 *)m1.ptr, m1.ld, m1.batch, M, K, nmats)) return rc; }
+            if (trans) { if (int rc = pad_copy(ctx, ap, Kp, a_sz, Kp, Mp, (const wg16_elem_t *)m1.ptr, m1.ld, m1.batch, K, M, nmats)) return rc; }
+            else { if (int rc = pad_copy(ctx, ap, Mp, a_sz, Mp, Kp, (const wg16_elem_t *)m1.ptr, m1.ld, m1.batch, M, K, nmats)) return rc; }
             a2 = wgk_mat{ ap, trans ? Kp : Mp, a_sz };
         }
         if (!b_ok) {
-            if (int rc = pad_copy(ctx, bp, Kp, b_sz, Kp, N, (const _Float16 *)m2.ptr, m2.ld, m2.batch, K, N, nmats)) return rc;
+            if (int rc = pad_copy(ctx, bp, Kp, b_sz, Kp, N, (const wg16_elem_t *)m2.ptr, m2.ld, m2.batch, K, N, nmats)) return rc;
             b2 = wgk_mat{ bp, Kp, b_sz };
         }
-        if (c_ok) return wgk_gemm_f16(ctx, trans, M, N, Kp, nmats, out, out_ld, out_batch, a2, b2, alpha, beta);
+        if (c_ok) return WG16_SYM(wgk_gemm_, )(ctx, trans, M, N, Kp, nmats, out, out_ld, out_batch, a2, b2, alpha, beta);
         if (beta != 0.f) // the padded output starts as a copy of the old one
-            if (int rc = pad_copy(ctx, cp, Mp, c_sz, Mp, N, (const _Float16 *)out, out_ld, out_batch, M, N, nmats)) return rc;
-        if (int rc = wgk_gemm_f16(ctx, trans, Mp, N, Kp, nmats, (__half *)cp, Mp, c_sz, a2, b2, alpha, beta)) return rc;
-        return pad_copy(ctx, (_Float16 *)out, out_ld, out_batch, M, N, cp, Mp, c_sz, M, N, nmats);
+            if (int rc = pad_copy(ctx, cp, Mp, c_sz, Mp, N, (const wg16_elem_t *)out, out_ld, out_batch, M, N, nmats)) return rc;
+        if (int rc = WG16_SYM(wgk_gemm_, )(ctx, trans, Mp, N, Kp, nmats, (wg16_ext_t *)cp, Mp, c_sz, a2, b2, alpha, beta)) return rc;
+        return pad_copy(ctx, (wg16_elem_t *)out, out_ld, out_batch, M, N, cp, Mp, c_sz, M, N, nmats);
     } else {
         g.tiles_m = (M + 63) / 64;
         g.tiles_n = (N + 63) / 64;
         g.nsplit = 1; g.k_per_split = K; g.part = nullptr;
         if (g.tiles_n > 65535) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: N too large for the generic f16 path");
-        wg_path(ctx, "f16.generic");
+        wg_path(ctx, WG16_TAG ".generic");
         if (int rc = generic_launch(ctx, trans, dim3(g.tiles_m, g.tiles_n, nmats), g)) return rc;
     }
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;
 }
 
+#ifndef WG_GEMM16_BF16 // (the planner and the context's calibration are shared by both element types: exported once, by the f16 build)
 // Host-side check of the planner (tests/test_abi_and_host.py; no device needed): the plan for `tiles` whole tiles of `stages` stages from the
 // relative slot rates rel8 (or the fixed test pattern), decoded for every workgroup id exactly as the kernel decodes it.
 // units[5 i .. 5 i + 4] = (tile, mode, first stage, stages, pair) of the i-th workgroup that has a unit.
@@ -1981,3 +1982,4 @@ extern "C" int wg_ctx_f16_balance_info(const wg_ctx *ctx, double *rel8, int *val
     if (balanced_launches) *balanced_launches = ctx->bal.epoch;
     return WG_OK;
 }
+#endif

@@ -9,14 +9,41 @@
 #include <utility>
 #include <vector>
 
-namespace wgf16 {
+// The element type of the 16-bit Gemm family is a compile-time switch. These sources (gemm_f16.hip, gemm_f16_t128.hip, gemm_f16_nt.hip, gemm_f16_generic.hip)
+// are compiled twice: as they are for f16, and -- included by gemm_bf16*.hip, which define WG_GEMM16_BF16 -- for bfloat16. Everything that moves data (LDS-DMA,
+// the transposing LDS reads, swizzles, the tile walk, split-K slabs) is the same at 16 bits; what differs is collected here: the element type (its conversions to
+// and from f32 are the compiler's: exact widening, one round-to-nearest-even narrowing -- v_cvt_pk_bf16_f32 for bf16), the MFMA opcode as builtin and as mnemonic,
+// the dtype handed to the shared staging / slab-reduce launchers, the tag prefix of the launch log and the prefix of every symbol the two builds would share.
+#ifdef WG_GEMM16_BF16
+typedef __bf16 wg16_elem_t;
+typedef wg_bf16 wg16_ext_t;              // the 16-bit pointer type of the launchers' signatures (wg_internal.hpp)
+#define WG16_ID bf16
+#define WG16_TAG "bf16"
+#define WG16_DTYPE WG_BF16
+#define WG16_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
+#define WG16_MFMA_ASM "v_mfma_f32_16x16x32_bf16"
+#else
+typedef _Float16 wg16_elem_t;
+typedef __half wg16_ext_t;
+#define WG16_ID f16
+#define WG16_TAG "f16"
+#define WG16_DTYPE WG_F16
+#define WG16_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16
+#define WG16_MFMA_ASM "v_mfma_f32_16x16x32_f16"
+#endif
+#define WG16_CAT3_(a, b, c) a##b##c
+#define WG16_CAT3(a, b, c) WG16_CAT3_(a, b, c)
+#define WG16_SYM(pre, post) WG16_CAT3(pre, WG16_ID, post) // WG16_SYM(gemm_, _m16_kernel): gemm_f16_m16_kernel | gemm_bf16_m16_kernel
+#define WG16_NS WG16_SYM(wg, )                             // the namespace of the build: wgf16 | wgbf16
+
+namespace WG16_NS {
 
 
 #ifndef WG_ABLATE
 #define WG_ABLATE 0 // timing experiments only: 1 = no barrier, 2 = no DMA, 4 = no LDS reads, 8 = (unused), 16 = no lane swaps, 32 = no epilogue stores (bitmask); results are garbage
 #endif
 
-typedef _Float16 half8_t __attribute__((ext_vector_type(8)));
+typedef wg16_elem_t half8_t __attribute__((ext_vector_type(8)));
 // The same 16 bytes at an address in GLOBAL memory that is only element-aligned (an operand view at an odd offset or with an odd leading dimension):
 // the target runs the memory pipeline in unaligned-access mode -- one global_load / global_store_dwordx4 either way, at the aligned rate for 4-byte offsets and
 // 0.9 of it for 2-byte ones (tools/cpp/unaligned_probe.hip, unaligned_dma_probe.hip; profiles/r06_unaligned_probe.txt) -- and the type says what is really known.
@@ -95,9 +122,9 @@ struct PanelArgs {
 };
 
 struct GemmArgs {
-    const _Float16 *a; uint32_t lda; uint64_t a_batch;
-    const _Float16 *b; uint32_t ldb; uint64_t b_batch;
-    _Float16 *c; uint32_t ldc; uint64_t c_batch;
+    const wg16_elem_t *a; uint32_t lda; uint64_t a_batch;
+    const wg16_elem_t *b; uint32_t ldb; uint64_t b_batch;
+    wg16_elem_t *c; uint32_t ldc; uint64_t c_batch;
     uint32_t M, N, K;
     uint32_t tiles_m, tiles_n;
     // split-K: grid.y = nmats * nsplit, workgroup (z, s) covers K range s and writes an f32 slab of `part` ([z][s][N][M])

@@ -4,7 +4,7 @@
 // initial value, gemm_f16.hip m16_tile), and shorter K runs on the 128 x 128 kernel or on zero-padded copies.
 #include "gemm_f16_common.hpp"
 
-namespace wgf16 {
+namespace WG16_NS {
 namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -12,13 +12,13 @@ namespace {
 // Same numerics contract (exact f16 products, f32 accumulation, one rounding); only the summation order differs.
 // ---------------------------------------------------------------------------------------------------------------
 template <bool TRANS_A>
-__global__ __launch_bounds__(256) void gemm_f16_generic_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256) void WG16_SYM(gemm_, _generic_kernel)(GemmArgs g) {
     __shared__ float As[16][65];
     __shared__ float Bs[16][65];
     const uint32_t z = blockIdx.z;
-    const _Float16 *A = g.a + z * g.a_batch;
-    const _Float16 *B = g.b + z * g.b_batch;
-    _Float16 *C = g.c + z * g.c_batch;
+    const wg16_elem_t *A = g.a + z * g.a_batch;
+    const wg16_elem_t *B = g.b + z * g.b_batch;
+    wg16_elem_t *C = g.c + z * g.c_batch;
     const uint32_t m0 = blockIdx.x * 64u, n0 = blockIdx.y * 64u;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4; // thread owns rows 4tx..4tx+3, cols 4ty..4ty+3
     float acc[4][4] = {};
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void gemm_f16_generic_kernel(GemmArgs g) {
             if (m < g.M) {
                 float r = g.alpha == 1.f ? acc[p][q] : g.alpha * acc[p][q];
                 if (g.beta != 0.f) r = fmaf(g.beta, (float)C[(uint64_t)n * g.ldc + m], r);
-                C[(uint64_t)n * g.ldc + m] = (_Float16)r;
+                C[(uint64_t)n * g.ldc + m] = (wg16_elem_t)r;
             }
         }
     }
@@ -72,8 +72,8 @@ __global__ __launch_bounds__(256) void gemm_f16_generic_kernel(GemmArgs g) {
 } // namespace
 
 int generic_launch(wg_ctx *ctx, bool trans, dim3 grid, const GemmArgs &g) {
-    if (trans) hipLaunchKernelGGL(gemm_f16_generic_kernel<true>, grid, dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL(gemm_f16_generic_kernel<false>, grid, dim3(256), 0, ctx->stream, g);
+    if (trans) hipLaunchKernelGGL(WG16_SYM(gemm_, _generic_kernel)<true>, grid, dim3(256), 0, ctx->stream, g);
+    else hipLaunchKernelGGL(WG16_SYM(gemm_, _generic_kernel)<false>, grid, dim3(256), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;
 }

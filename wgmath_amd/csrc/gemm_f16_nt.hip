@@ -17,7 +17,7 @@
 // Bound: MFMA (2.5 PFLOP/s dense), in practice the package power cap, as the other f16 kernels.
 #include "gemm_f16_common.hpp"
 
-namespace wgf16 {
+namespace WG16_NS {
 namespace {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -39,7 +39,7 @@ __device__ __forceinline__ void nt_dma(uint32_t voff, const void *sbase) {
     asm volatile("global_load_lds_dwordx4 %0, %1 offset:%c2" ::"v"(voff), "s"(sbase), "i"(IMM));
 }
 
-__global__ __launch_bounds__(256, 1) void gemm_f16_nt_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256, 1) void WG16_SYM(gemm_, _nt_kernel)(GemmArgs g) {
     __shared__ __attribute__((aligned(16))) char smem[128 * 1024];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -52,9 +52,9 @@ __global__ __launch_bounds__(256, 1) void gemm_f16_nt_kernel(GemmArgs g) {
     auto sc64 = [](uint64_t v) -> uint64_t { // (64-bit products run on the vector unit even when uniform: back to scalar registers by hand -- they end up in scalar operands of the DMA asm)
         return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
     };
-    const _Float16 *A = g.a + sc64((uint64_t)z * g.a_batch) + m0;
-    const _Float16 *B = g.b + sc64((uint64_t)z * g.b_batch) + n0;
-    _Float16 *C = g.c + sc64((uint64_t)z * g.c_batch);
+    const wg16_elem_t *A = g.a + sc64((uint64_t)z * g.a_batch) + m0;
+    const wg16_elem_t *B = g.b + sc64((uint64_t)z * g.b_batch) + n0;
+    wg16_elem_t *C = g.c + sc64((uint64_t)z * g.c_batch);
     float alpha = g.alpha, beta = g.beta;
     uint32_t ldc = g.ldc;
     asm volatile("" : "+s"(C), "+s"(alpha), "+s"(beta), "+s"(ldc)); // (pinned now: scalar loads in front of the loop would share lgkmcnt with its LDS reads)
@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f16_nt_kernel(GemmArgs g) {
         nt_static_for<64>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             constexpr int t = j >> 3, u = j & 7;
-            acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, a_r[HS][t]), __builtin_bit_cast(half8_t, b_r[HS][u]), acc[t][u], 0, 0, 0);
+            acc[t][u] = WG16_MFMA(__builtin_bit_cast(half8_t, a_r[HS][t]), __builtin_bit_cast(half8_t, b_r[HS][u]), acc[t][u], 0, 0, 0);
             if constexpr ((j & 3) != 3 && 3 * (j >> 2) + (j & 3) < kOps) frag(3 * (j >> 2) + (j & 3), HS ^ 1); // three fragment ops in every four slots (0 .. 41)
             if constexpr (j == NT_DO - 1) nt_set_m0(lds_a_wave + rD);
             if constexpr (j == NT_DO + 4 * NT_DS - 5) { lb = lds_b_wave + rD; asm volatile("" : "+s"(lb)); }
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f16_nt_kernel(GemmArgs g) {
     for (int u = 0; u < 8; ++u) {
         const uint32_t col = n0 + 128u * wn + 32u * (uint32_t)(u >> 1) + 8u * ca + 4u * ((uint32_t)(u & 1) ^ (ca & 1u)) + ((uint32_t)i16 & 3u);
         if (!full_tile && col >= g.N) continue;
-        _Float16 *cc = C + (uint64_t)col * ldc + row0;
+        wg16_elem_t *cc = C + (uint64_t)col * ldc + row0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             if (!(full_tile || row0 + 32 * p < g.M)) continue; // 8 consecutive rows, all in or all out (M % 8 == 0)
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f16_nt_kernel(GemmArgs g) {
             }
             half8_t v;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = (_Float16)r[q];
+            for (int q = 0; q < 8; ++q) v[q] = (wg16_elem_t)r[q];
             *reinterpret_cast<half8_u *>(cc + 32 * p) = v;
         }
     }
@@ -223,8 +223,8 @@ __global__ __launch_bounds__(256, 1) void gemm_f16_nt_kernel(GemmArgs g) {
 } // namespace
 
 // WG_ERR_UNSUPPORTED (no message): not a product this kernel takes -- the caller goes the transposed-copy way.
-static int nt_launch(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, _Float16 *out, uint32_t out_ld, uint64_t out_batch, const _Float16 *a, uint32_t lda,
-              uint64_t a_batch, const _Float16 *b, uint32_t ldb, uint64_t b_batch, float alpha, float beta) {
+static int nt_launch(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_elem_t *out, uint32_t out_ld, uint64_t out_batch, const wg16_elem_t *a, uint32_t lda,
+              uint64_t a_batch, const wg16_elem_t *b, uint32_t ldb, uint64_t b_batch, float alpha, float beta) {
     if (M == 0 || N == 0 || nmats == 0) return WG_OK;
     // (any leading dimension, offset and batch stride: the LDS-DMA and the 16-byte stores take element-aligned addresses -- gemm_f16_common.hpp half8_u)
     if (M % 8u || N % 8u || K % 64u || K < 256u || nmats > 65535u) return WG_ERR_UNSUPPORTED;
@@ -253,19 +253,19 @@ static int nt_launch(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t n
         t.part = nullptr;
         const uint64_t tt = (uint64_t)t.tiles_m * t.tiles_n;
         if (tt > 0x7fffffffull) return WG_ERR_UNSUPPORTED;
-        wg_path(ctx, "f16.t128nc/tm=%d", tall ? 256 : 128);
+        wg_path(ctx, WG16_TAG ".t128nc/tm=%d", tall ? 256 : 128);
         return t128_launch_nt(ctx, dim3((uint32_t)tt, nmats), t, tall ? 256 : 128);
     }
-    wg_path(ctx, "f16.nt");
-    hipLaunchKernelGGL(gemm_f16_nt_kernel, dim3((uint32_t)tiles, nmats), dim3(256), 0, ctx->stream, g);
+    wg_path(ctx, WG16_TAG ".nt");
+    hipLaunchKernelGGL(WG16_SYM(gemm_, _nt_kernel), dim3((uint32_t)tiles, nmats), dim3(256), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;
 }
 
 } // namespace wgf16
 
-int wgk_gemm_f16_nt(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, __half *out, uint32_t out_ld, uint64_t out_batch, wgk_mat a_mcontig, wgk_mat b_ncontig,
+int WG16_SYM(wgk_gemm_, _nt)(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_ext_t *out, uint32_t out_ld, uint64_t out_batch, wgk_mat a_mcontig, wgk_mat b_ncontig,
                     float alpha, float beta) {
-    return wgf16::nt_launch(ctx, M, N, K, nmats, (_Float16 *)out, out_ld, out_batch, (const _Float16 *)a_mcontig.ptr, a_mcontig.ld, a_mcontig.batch,
-                            (const _Float16 *)b_ncontig.ptr, b_ncontig.ld, b_ncontig.batch, alpha, beta);
+    return WG16_NS::nt_launch(ctx, M, N, K, nmats, (wg16_elem_t *)out, out_ld, out_batch, (const wg16_elem_t *)a_mcontig.ptr, a_mcontig.ld, a_mcontig.batch,
+                            (const wg16_elem_t *)b_ncontig.ptr, b_ncontig.ld, b_ncontig.batch, alpha, beta);
 }

@@ -29,7 +29,7 @@
 // the other workgroup covers the rest.
 #include "gemm_f16_common.hpp"
 
-namespace wgf16 {
+namespace WG16_NS {
 namespace {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -81,7 +81,7 @@ __device__ __forceinline__ void t_wait_keep_pieces(int n) { // s_waitcnt's count
 // is the 256 x 256 form). B then takes column-major A's path: pieces = k-quads of 256-byte [4 k][32 n] blocks, swap-free transposing reads, N tile 2 p' + tb of the wave
 // holding column 32 p' + 8 a + 4 (tb ^ (a & 1)) + e for lane i16 = 4 a + e (the epilogue's column index).
 template <bool TRANS_A, int TM, bool B_NC = false>
-__global__ __launch_bounds__(256, 2) void gemm_f16_t128_kernel(GemmArgs g) {
+__global__ __launch_bounds__(256, 2) void WG16_SYM(gemm_, _t128_kernel)(GemmArgs g) {
     static_assert(!(B_NC && TRANS_A) && (!B_NC || WG_NN_NOSWAP), "n-contiguous m2: Gemm only, on the swap-free read path");
     using Cfg = TCfg<TM>;
     constexpr int APW = Cfg::APW, PPW = Cfg::PPW, RB = Cfg::RB, T_SLOT = Cfg::SLOT, T_RING = Cfg::RING, MT = Cfg::MT, MP = Cfg::MP;
@@ -106,8 +106,8 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_t128_kernel(GemmArgs g) {
     const uint32_t rem = K_loc & 63u;
     K_loc -= rem;
     const uint32_t rem_dk = K_loc; // the remainder's first k, relative to k_begin
-    const _Float16 *A = g.a + z * g.a_batch + (TRANS_A ? (uint64_t)k_begin : (uint64_t)k_begin * g.lda);
-    const _Float16 *B = g.b + z * g.b_batch + (B_NC ? (uint64_t)k_begin * g.ldb : (uint64_t)k_begin);
+    const wg16_elem_t *A = g.a + z * g.a_batch + (TRANS_A ? (uint64_t)k_begin : (uint64_t)k_begin * g.lda);
+    const wg16_elem_t *B = g.b + z * g.b_batch + (B_NC ? (uint64_t)k_begin * g.ldb : (uint64_t)k_begin);
 
     // ---- DMA addressing: per half-stage this wave stages pieces P = 2 wave + q (q = 0, 1) of A and of B; a piece = 1 KiB of LDS
     // (64 lanes x 16 bytes). k-contiguous operands (B; op(A) for TN): piece P = rows 16P..16P+15 of 64 bytes (32 k), lane -> row
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_t128_kernel(GemmArgs g) {
     // instruction offset's 4095 bytes from the region's start: a second M0 value, B_IMM0 = 0; TM = 128: one M0, B_IMM0 = 2048, as before)
     constexpr int B_IMM0 = APW == 2 ? 2048 : 0;
     uint32_t a_voff[APW], b_voff[2];
-    const _Float16 *a_base, *b_base = B_NC ? B + n0 : B + (uint64_t)n0 * g.ldb;
+    const wg16_elem_t *a_base, *b_base = B_NC ? B + n0 : B + (uint64_t)n0 * g.ldb;
     if constexpr (TRANS_A) a_base = A + (uint64_t)m0 * g.lda; else a_base = A + m0;
 #pragma unroll
     for (int q = 0; q < APW; ++q) {
@@ -319,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_t128_kernel(GemmArgs g) {
             constexpr int j = decltype(jc)::value;
             constexpr int t = j >> 2, u = j & 3;
             if (!(WG_T128_ABLATE & 1))
-            acc[t][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(half8_t, a_r[SET][t]), b_f[SET][u], acc[t][u], 0, 0, 0);
+            acc[t][u] = WG16_MFMA(__builtin_bit_cast(half8_t, a_r[SET][t]), b_f[SET][u], acc[t][u], 0, 0, 0);
             if (next_f() && !(WG_T128_ABLATE & 1)) {
                 if constexpr (TRANS_A) {
                     if constexpr (j < kOps) frag_op(sl, j, SET ^ 1);
@@ -392,13 +392,13 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_t128_kernel(GemmArgs g) {
         }
         return;
     }
-    _Float16 *C = g.c + z * g.c_batch;
+    wg16_elem_t *C = g.c + z * g.c_batch;
     const float alpha = g.alpha, beta = g.beta;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const uint32_t col = n0 + 64u * wn + col_in_wave(u);
         if (!full_tile && col >= g.N) continue;
-        _Float16 *cc = C + (uint64_t)col * g.ldc + row0;
+        wg16_elem_t *cc = C + (uint64_t)col * g.ldc + row0;
 #pragma unroll
         for (int p = 0; p < MP; ++p) {
             if (!(full_tile || row0 + 32 * p < g.M)) continue; // 8 consecutive rows, all in or all out (M % 8 == 0)
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_t128_kernel(GemmArgs g) {
             }
             half8_t v;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = (_Float16)r[q];
+            for (int q = 0; q < 8; ++q) v[q] = (wg16_elem_t)r[q];
             *reinterpret_cast<half8_u *>(cc + 32 * p) = v;
         }
     }
@@ -429,18 +429,18 @@ __global__ __launch_bounds__(256, 2) void gemm_f16_t128_kernel(GemmArgs g) {
 
 // the B_NC instances (row-major GemmTr on mid-size outputs: gemm_f16_nt.hip's launcher). Whole K per workgroup, K % 64 == 0.
 int t128_launch_nt(wg_ctx *ctx, dim3 grid, const GemmArgs &g, int tm) {
-    if (tm == 256) hipLaunchKernelGGL((gemm_f16_t128_kernel<false, 256, true>), grid, dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL((gemm_f16_t128_kernel<false, 128, true>), grid, dim3(256), 0, ctx->stream, g);
+    if (tm == 256) hipLaunchKernelGGL((WG16_SYM(gemm_, _t128_kernel)<false, 256, true>), grid, dim3(256), 0, ctx->stream, g);
+    else hipLaunchKernelGGL((WG16_SYM(gemm_, _t128_kernel)<false, 128, true>), grid, dim3(256), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;
 }
 
 int t128_launch(wg_ctx *ctx, bool trans, dim3 grid, const GemmArgs &g, int tm) {
     if (tm == 256) {
-        if (trans) hipLaunchKernelGGL((gemm_f16_t128_kernel<true, 256>), grid, dim3(256), 0, ctx->stream, g);
-        else hipLaunchKernelGGL((gemm_f16_t128_kernel<false, 256>), grid, dim3(256), 0, ctx->stream, g);
-    } else if (trans) hipLaunchKernelGGL((gemm_f16_t128_kernel<true, 128>), grid, dim3(256), 0, ctx->stream, g);
-    else hipLaunchKernelGGL((gemm_f16_t128_kernel<false, 128>), grid, dim3(256), 0, ctx->stream, g);
+        if (trans) hipLaunchKernelGGL((WG16_SYM(gemm_, _t128_kernel)<true, 256>), grid, dim3(256), 0, ctx->stream, g);
+        else hipLaunchKernelGGL((WG16_SYM(gemm_, _t128_kernel)<false, 256>), grid, dim3(256), 0, ctx->stream, g);
+    } else if (trans) hipLaunchKernelGGL((WG16_SYM(gemm_, _t128_kernel)<true, 128>), grid, dim3(256), 0, ctx->stream, g);
+    else hipLaunchKernelGGL((WG16_SYM(gemm_, _t128_kernel)<false, 128>), grid, dim3(256), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;
 }

@@ -12,6 +12,7 @@
 // stage was 50-70 % slower (the waves drift with memory latency); a 16-wide MFMA variant for N <= 16 changed nothing THEN (round 1, a slower stream) and is
 // the shipped form for N <= 16 since round 5 (W16 below): with the stream at 5.3 TB/s the 32-wide MFMAs kept the matrix pipe busy 58 % of the time and the clock at 1.9 GHz.
 #include "wg_internal.hpp"
+#include "gemm_f16_common.hpp" // the 16-bit element-type switch (the T = 16-bit instance)
 #include <cstdlib>
 #include <type_traits>
 
@@ -86,10 +87,19 @@ __device__ __forceinline__ void tr_set_m0(uint32_t lds_dst) { asm volatile("s_mo
 // 16-byte chunk is the 8 halves v_mfma_f32_16x16x32_f16 takes from it (k = 8 kq .. 8 kq + 7 of a 32-k block: chunk kq + 4 j is block j), f32 accumulation, one
 // rounding at the store (split partials stay f32). What it is for: f16 GemvTr with 3 .. 16 right-hand sides / f16 GemmTr with few columns, which the tiled
 // f16 kernels ran at 3.9 TB/s (65536 x 4096 x 8: 138 us, vendor 115).
-typedef _Float16 sk_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 sk_h4 __attribute__((ext_vector_type(4)));
+// The 16-bit form's element type is the switch of the 16-bit Gemm family (gemm_f16_common.hpp: wg16_elem_t, WG16_MFMA, WG16_TAG, WG16_DTYPE, WG16_SYM):
+// gemm_bf16_skinny.hip defines WG_GEMM16_BF16 and includes this file, which then yields the bfloat16 instance alone, under its own kernel and launcher names.
+// (The kernel's name is the one thing the switch cannot spell: the f16 instance is an instance of gemm_f32_skinny_kernel.)
+#ifdef WG_GEMM16_BF16
+#define WG_SKINNY_KERNEL16 gemm_bf16_skinny_kernel
+#else
+#define WG_SKINNY_KERNEL16 gemm_f32_skinny_kernel
+#endif
+typedef wg16_elem_t sk_16;
+typedef sk_16 sk_h8 __attribute__((ext_vector_type(8)));
+typedef sk_16 sk_h4 __attribute__((ext_vector_type(4)));
 template <bool TRANS_A, int NT, bool B_KMAJ = false, bool W16 = false, typename T = float>
-__global__ __launch_bounds__(256, 1) void gemm_f32_skinny_kernel(SkinnyArgs g) {
+__global__ __launch_bounds__(256, 1) void WG_SKINNY_KERNEL16(SkinnyArgs g) {
     static_assert(!W16 || NT == 1, "the 16-wide form has one column tile");
     constexpr bool F16 = sizeof(T) == 2;
     static_assert(!F16 || (TRANS_A && W16 && !B_KMAJ), "f16: GemmTr, N <= 16, k-contiguous m2");
@@ -222,7 +232,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32_skinny_kernel(SkinnyArgs g) {
                     }
                 }
 #pragma unroll
-                for (int t = 0; t < 2; ++t) acc16[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[t], bh, acc16[t], 0, 0, 0);
+                for (int t = 0; t < 2; ++t) acc16[t] = WG16_MFMA(ah[t], bh, acc16[t], 0, 0, 0);
             }
             __builtin_amdgcn_s_waitcnt(0xc07f);
             return;
@@ -348,13 +358,13 @@ __global__ __launch_bounds__(256, 1) void gemm_f32_skinny_kernel(SkinnyArgs g) {
                 float4 v = make_float4(acc16[t][0], acc16[t][1], acc16[t][2], acc16[t][3]);
                 if constexpr (F16) {
                     if (!direct) { put4(col, row, v); continue; } // f32 partial slab
-                    _Float16 *dst = reinterpret_cast<_Float16 *>(g.c) + z * g.c_batch + (uint64_t)col * g.ldc + row;
+                    sk_16 *dst = reinterpret_cast<sk_16 *>(g.c) + z * g.c_batch + (uint64_t)col * g.ldc + row;
                     if (g.alpha != 1.f) { v.x *= g.alpha; v.y *= g.alpha; v.z *= g.alpha; v.w *= g.alpha; }
                     if (g.beta != 0.f) {
                         const sk_h4 o = *reinterpret_cast<const sk_h4 *>(dst);
                         v.x = fmaf(g.beta, (float)o[0], v.x); v.y = fmaf(g.beta, (float)o[1], v.y); v.z = fmaf(g.beta, (float)o[2], v.z); v.w = fmaf(g.beta, (float)o[3], v.w);
                     }
-                    const sk_h4 hv = { (_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w };
+                    const sk_h4 hv = { (sk_16)v.x, (sk_16)v.y, (sk_16)v.z, (sk_16)v.w };
                     *reinterpret_cast<sk_h4 *>(dst) = hv;
                 } else put4(col, row, v);
             }
@@ -390,6 +400,7 @@ __global__ __launch_bounds__(256, 1) void gemm_f32_skinny_kernel(SkinnyArgs g) {
 
 } // namespace
 
+#ifndef WG_GEMM16_BF16
 // out = alpha * m1 * m2 + beta * out for N <= 64 (NN only). Returns WG_ERR_UNSUPPORTED-free: the caller checks applicability.
 int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
                         wgk_mat m1, wgk_mat m2, float alpha, float beta, uint32_t out_row_stride, bool m2_kmajor, uint32_t ns_force) {
@@ -447,9 +458,12 @@ int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_
     return wg_splitk_reduce(ctx, g.part, ns, M, N, nmats, WG_F32, out, out_ld, out_batch, alpha, beta);
 }
 
+#endif // !WG_GEMM16_BF16
+
 // f16 GemmTr with N <= 16 (f16 GemvTr with a few right-hand sides arrives here through wgk_gemm_f16): out = alpha * m1^T * m2 + beta * out, m1 stored K x M and m2
 // K x N, both k-contiguous. The caller (wgk_gemm_f16) has checked: K % 8 == 0, leading dimensions % 8 == 0, 16-byte aligned bases, 32-bit offsets in range.
-int wgk_gemm_f16_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, __half *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
+int WG16_SYM(wgk_gemm_, _skinny)(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_ext_t *out,
+                        uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
                         float alpha, float beta) {
     const int cus = ctx->compute_units > 0 ? ctx->compute_units : 256;
     const uint32_t row_blocks = (M + 127u) / 128u;
@@ -476,9 +490,9 @@ int wgk_gemm_f16_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_
     g.part = (float *)ws; g.M = M; g.N = N; g.K = K; g.nsplit = ns; g.k_per_split = kps; g.npanels = 1;
     g.rot = (uint64_t)(ns > 1 ? kps : K) * N * 2u <= (256u << 10) ? 1u : 0u;
     g.a_nt = (uint64_t)M * K * 2u >= (384ull << 20) ? 1u : 0u;
-    wg_path(ctx, "f16.skinny/ns=%u", ns);
-    hipLaunchKernelGGL((gemm_f32_skinny_kernel<true, 1, false, true, _Float16>), dim3(row_blocks, ns, nmats), dim3(256), 0, ctx->stream, g);
+    wg_path(ctx, WG16_TAG ".skinny/ns=%u", ns);
+    hipLaunchKernelGGL((WG_SKINNY_KERNEL16<true, 1, false, true, sk_16>), dim3(row_blocks, ns, nmats), dim3(256), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
     if (ns == 1) return WG_OK;
-    return wg_splitk_reduce(ctx, g.part, ns, M, N, nmats, WG_F16, out, out_ld, out_batch, alpha, beta);
+    return wg_splitk_reduce(ctx, g.part, ns, M, N, nmats, WG16_DTYPE, out, out_ld, out_batch, alpha, beta);
 }

@@ -53,22 +53,29 @@ __device__ __forceinline__ void fma4(float4 &acc, float4 a, float s) {
 }
 // Element types: f32 (the reference's), and f16 as this build's extension (f16 matrix / vectors, f32 accumulation in the same per-lane +
 // butterfly order, one rounding when the result is stored; split partials stay f32). Four consecutive elements as floats:
-typedef _Float16 wg_h4 __attribute__((ext_vector_type(4)));
+// (bf16, the second 16-bit extension: the same kernels with the other widening / narrowing -- wg_internal.hpp wg_bf16)
 __device__ __forceinline__ float4 load4s(const float *p) { return ld_stream(reinterpret_cast<const float4 *>(p)); } // streaming (matrix)
-__device__ __forceinline__ float4 load4s(const _Float16 *p) {
-    const wg_h4 v = GEMV_NT ? __builtin_nontemporal_load(reinterpret_cast<const wg_h4 *>(p)) : *reinterpret_cast<const wg_h4 *>(p);
-    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
 __device__ __forceinline__ float4 load4(const float *p) { return *reinterpret_cast<const float4 *>(p); } // cached (vector)
-__device__ __forceinline__ float4 load4(const _Float16 *p) {
-    const wg_h4 v = *reinterpret_cast<const wg_h4 *>(p);
-    return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-}
 __device__ __forceinline__ void store4(float *d, float4 s) { *reinterpret_cast<float4 *>(d) = s; }
-__device__ __forceinline__ void store4(_Float16 *d, float4 s) {
-    const wg_h4 v = { (_Float16)s.x, (_Float16)s.y, (_Float16)s.z, (_Float16)s.w };
-    *reinterpret_cast<wg_h4 *>(d) = v;
-}
+#define WG_GEMV_ELEM16(H)                                                                                                             \
+    __device__ __forceinline__ float4 load4s(const H *p) {                                                                            \
+        typedef H h4 __attribute__((ext_vector_type(4)));                                                                             \
+        const h4 v = GEMV_NT ? __builtin_nontemporal_load(reinterpret_cast<const h4 *>(p)) : *reinterpret_cast<const h4 *>(p);        \
+        return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);                                                       \
+    }                                                                                                                                 \
+    __device__ __forceinline__ float4 load4(const H *p) {                                                                             \
+        typedef H h4 __attribute__((ext_vector_type(4)));                                                                             \
+        const h4 v = *reinterpret_cast<const h4 *>(p);                                                                                \
+        return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);                                                       \
+    }                                                                                                                                 \
+    __device__ __forceinline__ void store4(H *d, float4 s) {                                                                          \
+        typedef H h4 __attribute__((ext_vector_type(4)));                                                                             \
+        const h4 v = { (H)s.x, (H)s.y, (H)s.z, (H)s.w };                                                                              \
+        *reinterpret_cast<h4 *>(d) = v;                                                                                               \
+    }
+WG_GEMV_ELEM16(_Float16)
+WG_GEMV_ELEM16(wg_bf16)
+#undef WG_GEMV_ELEM16
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
     for (int s = 32; s >= 1; s >>= 1) x += __shfl_xor(x, s, 64);
@@ -261,14 +268,14 @@ __global__ __launch_bounds__(kThreads) void gemv_t_kernel(GemvArgsT<T> a) {
 #ifndef WG_GEMVT_ROT
 #define WG_GEMVT_ROT 0 // 1: column c starts its sweep (c * 5) blocks of rows in and wraps around (de-phases the columns' streams)
 #endif
-typedef _Float16 wg_h8 __attribute__((ext_vector_type(8)));
-// E consecutive elements as floats (E = 4: load4 / load4s; E = 8: f16 only, one 16-byte load)
+// E consecutive elements as floats (E = 4: load4 / load4s; E = 8: the 16-bit types only, one 16-byte load)
 template <int E, typename T> struct RowPiece { float f[E]; };
 template <int E, typename T>
 __device__ __forceinline__ RowPiece<E, T> piece_stream(const T *p) {
     RowPiece<E, T> o;
     if constexpr (E == 4) { const float4 v = load4s(p); o.f[0] = v.x; o.f[1] = v.y; o.f[2] = v.z; o.f[3] = v.w; }
     else {
+        typedef T wg_h8 __attribute__((ext_vector_type(8)));
         const wg_h8 v = GEMV_NT ? __builtin_nontemporal_load(reinterpret_cast<const wg_h8 *>(p)) : *reinterpret_cast<const wg_h8 *>(p);
 #pragma unroll
         for (int i = 0; i < 8; ++i) o.f[i] = (float)v[i];
@@ -280,6 +287,7 @@ __device__ __forceinline__ RowPiece<E, T> piece_cached(const T *p) {
     RowPiece<E, T> o;
     if constexpr (E == 4) { const float4 v = load4(p); o.f[0] = v.x; o.f[1] = v.y; o.f[2] = v.z; o.f[3] = v.w; }
     else {
+        typedef T wg_h8 __attribute__((ext_vector_type(8)));
         const wg_h8 v = *reinterpret_cast<const wg_h8 *>(p);
 #pragma unroll
         for (int i = 0; i < 8; ++i) o.f[i] = (float)v[i];
@@ -933,7 +941,7 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
              void *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v) {
     if (rows_out == 0 || nrhs == 0 || nmats == 0) return WG_OK;
     wg_path(ctx, "gemv>");
-    if (uses_t_lds(ctx, trans, rows_out, k, nrhs, nmats, dtype == WG_F16 ? 2u : 4u)) {
+    if (uses_t_lds(ctx, trans, rows_out, k, nrhs, nmats, (uint32_t)wg_dtype_size(dtype))) {
         return gemv_t_lds_launch<float>(ctx, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
     }
     if (dtype == WG_F16) {
@@ -944,6 +952,12 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
             return wgk_gemm_f16(ctx, trans, rows_out, nrhs, k, nmats, (__half *)out, out_ld, out_batch, m, v, 1.f, 0.f);
         wg_path(ctx, "f16.gemv");
         return gemv_launch<_Float16>(ctx, trans, rows_out, k, nrhs, nmats, (_Float16 *)out, out_ld, out_batch, m, v);
+    }
+    if (dtype == WG_BF16) { // (extension, as f16: the same kernels and the same dispatch on bfloat16 elements)
+        if (nrhs > (uint32_t)kMaxRhs || few_rhs_as_gemm(trans, true, rows_out, k, nrhs, 2u))
+            return wgk_gemm_bf16(ctx, trans, rows_out, nrhs, k, nmats, (wg_bf16 *)out, out_ld, out_batch, m, v, 1.f, 0.f);
+        wg_path(ctx, "bf16.gemv");
+        return gemv_launch<wg_bf16>(ctx, trans, rows_out, k, nrhs, nmats, (wg_bf16 *)out, out_ld, out_batch, m, v);
     }
     // 9 .. 64 right-hand sides are a Gemm with few columns: one pass over the matrix on the matrix cores (gemm_f32_skinny.hip) instead of
     // one GEMV pass per 8 columns. (The 32-bit DMA offsets of that kernel must suffice for both operands, in both variants.)

@@ -29,6 +29,7 @@ constexpr int kThreads = 256, kWaves = 4;
 template <typename T> struct Elt;
 template <> struct Elt<float> { static constexpr int E = 4, ES = 4; };
 template <> struct Elt<_Float16> { static constexpr int E = 8, ES = 2; };
+template <> struct Elt<wg_bf16> { static constexpr int E = 8, ES = 2; };
 
 typedef uint32_t wg_u32x4 __attribute__((ext_vector_type(4)));
 template <typename T>
@@ -36,7 +37,7 @@ __device__ __forceinline__ void to_floats(wg_u32x4 v, float (&f)[Elt<T>::E]) {
     if constexpr (Elt<T>::ES == 4) {
         f[0] = __uint_as_float(v.x); f[1] = __uint_as_float(v.y); f[2] = __uint_as_float(v.z); f[3] = __uint_as_float(v.w);
     } else {
-        typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+        typedef T h8 __attribute__((ext_vector_type(8)));
         const h8 h = __builtin_bit_cast(h8, v);
 #pragma unroll
         for (int e = 0; e < 8; ++e) f[e] = (float)h[e];
@@ -250,5 +251,6 @@ int wgk_gemv_any(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t R, uint32_t C
                  wgk_mat m, wgk_mat v) {
     if (R == 0 || C == 0 || nrhs == 0 || nmats == 0) return WG_OK;
     if (dtype == WG_F16) return launch_any<_Float16>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
+    if (dtype == WG_BF16) return launch_any<wg_bf16>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
     return launch_any<float>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
 }

@@ -10,6 +10,7 @@
 // IEEE-correct + - * / (no fast-math, correctly rounded division): results are bit-identical to the CPU.
 #include "wg_internal.hpp"
 
+
 namespace {
 
 enum { OP_ADD = 0, OP_SUB = 1, OP_MUL = 2, OP_DIV = 3, OP_COPY = 4, OP_AXPY = 5 /* a = fma(alpha, b, a): wg_axpy */ };
@@ -116,35 +117,45 @@ __global__ __launch_bounds__(kThreads) void op_assign_f32_vec(float *a0, const f
 
 // f16 (extension): computed in f32 and rounded once; for + - * / that equals the correctly rounded f16 result
 // (24 >= 2*11 + 2 significand bits, so the double rounding is innocuous).
-template <int OP>
-__device__ __forceinline__ __half apply_h(__half a, __half b, float alpha) {
+// bf16 (extension, likewise): widened exactly, computed in f32, rounded once (RNE). H: the 16-bit element type.
+__device__ __forceinline__ float widen(__half x) { return __half2float(x); }
+__device__ __forceinline__ float widen(wg_bf16 x) { return (float)x; }
+__device__ __forceinline__ __half narrow(float r, __half) { return __float2half_rn(r); }
+__device__ __forceinline__ wg_bf16 narrow(float r, wg_bf16) { return (wg_bf16)r; }
+template <int OP, typename H>
+__device__ __forceinline__ H apply_h(H a, H b, float alpha) {
     if constexpr (OP == OP_COPY) return b;
     else {
-        float r = apply<OP>(__half2float(a), __half2float(b), alpha);
+        float r = apply<OP>(widen(a), widen(b), alpha);
         // axpy: keep the f32 rounding of the fma (the stated contract, and what the float4-wide path does); without this
         // fence hipcc selects v_fma_mixlo_f16 on the scalar path, which rounds the exact result straight to f16.
         if constexpr (OP == OP_AXPY) asm volatile("" : "+v"(r));
-        return __float2half_rn(r);
+        return narrow(r, H{});
     }
 }
 
-struct alignas(16) half8 { __half h[8]; };
-struct alignas(2) half8_u { __half h[8]; }; // (the same 16 bytes at an element-aligned address)
+template <typename H> struct alignas(16) half8_of { H h[8]; };
+template <typename H> struct alignas(2) half8_u_of { H h[8]; }; // (the same 16 bytes at an element-aligned address)
 
-template <int OP, bool BU>
-__global__ __launch_bounds__(kThreads) void op_assign_f16_vec(__half *a0, const __half *b0, uint32_t head, uint32_t n8, uint32_t n, float alpha) {
+template <int OP, bool BU, typename H>
+__global__ __launch_bounds__(kThreads) void op_assign_f16_vec(H *a0, const H *b0, uint32_t head, uint32_t n8, uint32_t n, float alpha) {
+    using half8 = half8_of<H>;
+    using half8_u = half8_u_of<H>;
     if (blockIdx.x == 0) {
         const uint32_t body_end = head + 8u * n8;
         const uint32_t edge = head + (n - body_end);
         if (threadIdx.x < edge) {
             const uint32_t i = threadIdx.x < head ? threadIdx.x : body_end + (threadIdx.x - head);
-            __half vb = b0[i], va = vb;
+            H vb = b0[i], va = vb;
             if constexpr (OP != OP_COPY) va = a0[i];
             a0[i] = apply_h<OP>(va, vb, alpha);
         }
     }
     half8 *a = reinterpret_cast<half8 *>(a0 + head);
     const uint32_t stride = gridDim.x * kThreads; // flat grid: at most one trip
+    // (bf16 runs this loop as f16 does, one 16-byte piece per operand and lane. The chip has no packed bf16 arithmetic -- f16's Add is one v_pk_add_f16 per dword,
+    // bf16 widens, adds in f32 and narrows: 7 instructions -- but the stream hides it: two and four pieces per lane, consecutive or a stride apart, and the f32
+    // kernel's non-temporal hints were all measured slower than this form, which is level with f16: profiles/bf16_vs_f16.txt.)
     for (uint32_t i = blockIdx.x * kThreads + threadIdx.x; i < n8; i += stride) {
         half8 vb, va;
         if constexpr (BU) { const half8_u t = reinterpret_cast<const half8_u *>(b0 + head)[i]; __builtin_memcpy(&vb, &t, 16); }
@@ -179,15 +190,15 @@ int launch_f32(wg_ctx *ctx, float *a, const float *b, uint32_t n, float alpha) {
     return WG_OK;
 }
 
-template <int OP>
-int launch_f16(wg_ctx *ctx, __half *a, const __half *b, uint32_t n, float alpha) {
+template <int OP, typename H>
+int launch_f16(wg_ctx *ctx, H *a, const H *b, uint32_t n, float alpha) {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     uint32_t head = (uint32_t)(((16 - (pa & 15)) & 15) / 2);
     if (head > n) head = n;
     uint32_t n8 = (n - head) / 8;
     const uint32_t blocks = (n8 + kThreads - 1) / kThreads;
-    if ((pa & 15) == (pb & 15)) hipLaunchKernelGGL((op_assign_f16_vec<OP, false>), dim3(blocks ? blocks : 1), dim3(kThreads), 0, ctx->stream, a, b, head, n8, n, alpha);
-    else hipLaunchKernelGGL((op_assign_f16_vec<OP, true>), dim3(blocks ? blocks : 1), dim3(kThreads), 0, ctx->stream, a, b, head, n8, n, alpha);
+    if ((pa & 15) == (pb & 15)) hipLaunchKernelGGL((op_assign_f16_vec<OP, false, H>), dim3(blocks ? blocks : 1), dim3(kThreads), 0, ctx->stream, a, b, head, n8, n, alpha);
+    else hipLaunchKernelGGL((op_assign_f16_vec<OP, true, H>), dim3(blocks ? blocks : 1), dim3(kThreads), 0, ctx->stream, a, b, head, n8, n, alpha);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;
 }
@@ -198,8 +209,9 @@ int wgk_op_assign(wg_ctx *ctx, int op, wg_dtype dtype, void *a, const void *b, u
     if (n == 0) return WG_OK;
 #define WG_CASE(OPV)                                                                              \
     case OPV:                                                                                     \
-        return dtype == WG_F32 ? launch_f32<OPV>(ctx, (float *)a, (const float *)b, n, alpha)     \
-                               : launch_f16<OPV>(ctx, (__half *)a, (const __half *)b, n, alpha);
+        return dtype == WG_F32   ? launch_f32<OPV>(ctx, (float *)a, (const float *)b, n, alpha)       \
+               : dtype == WG_BF16 ? launch_f16<OPV>(ctx, (wg_bf16 *)a, (const wg_bf16 *)b, n, alpha)   \
+                                  : launch_f16<OPV>(ctx, (__half *)a, (const __half *)b, n, alpha);
     switch (op) {
         WG_CASE(OP_ADD)
         WG_CASE(OP_SUB)

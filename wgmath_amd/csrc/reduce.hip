@@ -43,9 +43,9 @@ __device__ __forceinline__ float4 load4(const float *p, bool nt) {
     if constexpr (AL) return nt ? wg_ld_nt(reinterpret_cast<const float4 *>(p)) : *reinterpret_cast<const float4 *>(p);
     else return wg_ld_u(p);
 }
-template <bool AL>
-__device__ __forceinline__ float4 load4(const _Float16 *p, bool nt) {
-    typedef _Float16 h4a __attribute__((ext_vector_type(4)));
+template <bool AL, typename H> // H: a 16-bit element type (_Float16, wg_bf16; bf16 is the same kind of extension: exact widening, one RNE rounding of the result)
+__device__ __forceinline__ float4 load4(const H *p, bool nt) {
+    typedef H h4a __attribute__((ext_vector_type(4)));
     typedef h4a __attribute__((aligned(2))) h4u;
     h4a v;
     if constexpr (AL) v = nt ? __builtin_nontemporal_load(reinterpret_cast<const h4a *>(p)) : *reinterpret_cast<const h4a *>(p);
@@ -311,6 +311,7 @@ static int reduce_fast_dispatch(wg_ctx *ctx, int op, const T *b, uint32_t n, T *
 
 int wgk_reduce_fast(wg_ctx *ctx, int op, wg_dtype dtype, const void *base, uint32_t n, void *result) {
     if (dtype == WG_F16) return reduce_fast_dispatch(ctx, op, (const _Float16 *)base, n, (_Float16 *)result);
+    if (dtype == WG_BF16) return reduce_fast_dispatch(ctx, op, (const wg_bf16 *)base, n, (wg_bf16 *)result);
     return reduce_fast_dispatch(ctx, op, (const float *)base, n, (float *)result);
 }
 
@@ -334,5 +335,6 @@ int wgk_reduce(wg_ctx *ctx, int op, wg_dtype dtype, const void *base, uint32_t n
     // Sum / Prod / SqNorm keep the reference's chains (wg_reduce_fast is the caller's explicit choice there).
     if ((op == R_MIN || op == R_MAX) && (uint64_t)ncols * nmats == 1 && n >= 65536u) return wgk_reduce_fast(ctx, op, dtype, base, n, results);
     if (dtype == WG_F16) return reduce_dispatch(ctx, op, (const _Float16 *)base, n, ncols, nmats, stride, stride_mat, (_Float16 *)results);
+    if (dtype == WG_BF16) return reduce_dispatch(ctx, op, (const wg_bf16 *)base, n, ncols, nmats, stride, stride_mat, (wg_bf16 *)results);
     return reduce_dispatch(ctx, op, (const float *)base, n, ncols, nmats, stride, stride_mat, (float *)results);
 }

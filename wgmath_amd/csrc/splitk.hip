@@ -4,6 +4,8 @@
 // kernel adds the slabs in ASCENDING s (deterministic; no atomics) and writes the result in the output's dtype and layout.
 #include "wg_internal.hpp"
 
+#include <type_traits>
+
 namespace {
 
 template <typename OUT>
@@ -23,7 +25,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
         s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
     }
     OUT *o = out + z * c_batch + (uint64_t)col * ldc + 4u * m4;
-    struct alignas(2) h4 { _Float16 v[4]; }; // (an f16 result at any element-aligned address: gemm_f16_common.hpp half8_u)
+    using E16 = std::conditional_t<sizeof(OUT) == 2, OUT, _Float16>; // the 16-bit element (f16 or bf16; unused by the f32 instance)
+    struct alignas(2) h4 { E16 v[4]; }; // (a 16-bit result at any element-aligned address: gemm_f16_common.hpp half8_u)
     if (alpha != 1.f) { s.x *= alpha; s.y *= alpha; s.z *= alpha; s.w *= alpha; }
     if (beta != 0.f) { // out = alpha * sum + beta * out (wg_gemm_ex); beta == 0 never reads `out`
         float4 c;
@@ -34,7 +37,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float *__restr
     if constexpr (sizeof(OUT) == 4) {
         wg_st_u(reinterpret_cast<float *>(o), s);
     } else {
-        h4 r = { { (_Float16)s.x, (_Float16)s.y, (_Float16)s.z, (_Float16)s.w } };
+        h4 r = { { (E16)s.x, (E16)s.y, (E16)s.z, (E16)s.w } };
         *reinterpret_cast<h4 *>(o) = r;
     }
     }
@@ -76,6 +79,7 @@ int wg_splitk_reduce(wg_ctx *ctx, const float *part, uint32_t nsplit, uint32_t M
     const dim3 grid((uint32_t)(blocks < 65536u ? (blocks ? blocks : 1u) : 65536u), 1, nmats), block(256); // (larger outputs: grid-stride trips)
     wg_path(ctx, "splitk.reduce/ns=%u", nsplit);
     if (dtype == WG_F32) hipLaunchKernelGGL(splitk_reduce_kernel<float>, grid, block, 0, ctx->stream, part, nsplit, M, N, (float *)out, ldc, c_batch, alpha, beta);
+    else if (dtype == WG_BF16) hipLaunchKernelGGL(splitk_reduce_kernel<wg_bf16>, grid, block, 0, ctx->stream, part, nsplit, M, N, (wg_bf16 *)out, ldc, c_batch, alpha, beta);
     else hipLaunchKernelGGL(splitk_reduce_kernel<_Float16>, grid, block, 0, ctx->stream, part, nsplit, M, N, (_Float16 *)out, ldc, c_batch, alpha, beta);
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;

@@ -40,7 +40,7 @@ int wgk_transpose(wg_ctx *ctx, wg_dtype dtype, uint32_t rows, uint32_t cols, uin
     if (dtype == WG_F32)
         hipLaunchKernelGGL(transpose_kernel<float>, grid, block, 0, ctx->stream, (const float *)src, ld_src, src_batch, (float *)dst, ld_dst,
                            dst_batch, rows, cols);
-    else
+    else // any 2-byte element (WG_F16, WG_BF16): the kernel only moves the 16 bits -- no arithmetic, so bf16 patterns pass through the _Float16 instance unchanged
         hipLaunchKernelGGL(transpose_kernel<_Float16>, grid, block, 0, ctx->stream, (const _Float16 *)src, ld_src, src_batch, (_Float16 *)dst,
                            ld_dst, dst_batch, rows, cols);
     WG_HIP_TRY(hipGetLastError());

@@ -157,7 +157,11 @@ __device__ __forceinline__ float4 wg_ld_u(const float *p) {
 }
 __device__ __forceinline__ void wg_st_u(float *p, float4 v) { *reinterpret_cast<wg_f4_u *>(p) = wg_f4{ v.x, v.y, v.z, v.w }; }
 
-static inline size_t wg_dtype_size(wg_dtype d) { return d == WG_F16 ? 2 : 4; }
+static inline size_t wg_dtype_size(wg_dtype d) { return d == WG_F32 ? 4 : 2; }
+// bfloat16 on the device (WG_BF16): the compiler's 2-byte type. (float)x is exact (the 16 bits become the high half), (wg_bf16)f is ONE round-to-nearest-even
+// (v_cvt_pk_bf16_f32: NaN stays a quiet NaN, +-Inf stays, a finite f32 past the largest bf16 becomes Inf, subnormals are kept on both sides). The element-type
+// templates of gemv.hip, gemv_any.hip, reduce.hip, op_assign.hip and splitk.hip take it like _Float16; host code only ever holds pointers to it.
+typedef __bf16 wg_bf16;
 
 // ---- kernel launchers (one per .hip file). All enqueue on ctx->stream and return a wg_status. -----
 // Pointers are already offset to the first element of the view; ld* / batch strides in elements.
@@ -198,6 +202,9 @@ int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_
 // f16 GemmTr with N <= 16 on the few-column streaming kernel (gemm_f32_skinny.hip, T = _Float16): HBM-bound, m1 read once
 int wgk_gemm_f16_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, __half *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
                         float alpha, float beta);
+// bfloat16 (gemm_bf16_skinny.hip: the same kernel source compiled for the other 16-bit element type)
+int wgk_gemm_bf16_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg_bf16 *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
+                         float alpha, float beta);
 // N-panels with arrival counters (comm.hip's one-launch-per-step sharded Gemm; gemm_f16_common.hpp PanelArgs): `out` is where the product's column 0
 // would sit if every panel were `cols` wide and the cube had one rank (i.e. panel 0's slot of this rank), leading dimension out_ld; panel p (first
 // column c0, np columns) lives at out + c0 * col_stride + slot_rows * (np - cols) ... see m16_tile. n_main panels of `cols` columns, then n_tail
@@ -217,6 +224,13 @@ static inline uint32_t wgk_panel_goal(uint32_t M, uint32_t np) { return 4u * ((M
 int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
                  __half *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha = 1.f, float beta = 0.f,
                  const wgk_panels *panels = nullptr);
+// bfloat16: the same launcher, sources and dispatch tree compiled for WG_BF16 (gemm_bf16.hip; gemm_f16_common.hpp's switch). No paneled form (comm.hip launches
+// bf16 panel by panel).
+int wgk_gemm_bf16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
+                  wg_bf16 *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha = 1.f, float beta = 0.f,
+                  const wgk_panels *panels = nullptr);
+int wgk_gemm_bf16_nt(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg_bf16 *out, uint32_t out_ld, uint64_t out_batch, wgk_mat a_mcontig, wgk_mat b_ncontig,
+                     float alpha = 1.f, float beta = 0.f);
 // gemm_f16_nt.hip: out (M x N, column-major) = a (M x K, m-contiguous: ld between k) * b (K x N, N-CONTIGUOUS: element (k, n) at n + k * ld) -- the row-major GemmTr in
 // column-major terms. WG_ERR_UNSUPPORTED without a message: not a product that kernel takes (the caller transposes `b` and calls wgk_gemm_f16).
 int wgk_gemm_f16_nt(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, __half *out, uint32_t out_ld, uint64_t out_batch, wgk_mat a_mcontig, wgk_mat b_ncontig,

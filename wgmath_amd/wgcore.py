@@ -22,14 +22,38 @@ import numpy as np
 from . import _lib
 from ._lib import ViewShapeC, check, lib
 
-_DT = {np.dtype(np.float32): _lib.WG_F32, np.dtype(np.float16): _lib.WG_F16}
+# bfloat16 (WG_BF16). NumPy has no such type: the element is a 2-byte record holding the 16 bits (`arr["bits"]`, or `arr.view(np.uint16)`), a dtype of its own --
+# distinct from float16 and uint16, hashable -- that is accepted wherever np.float16 is (TensorBuilder.build / build_init, GpuTensor.read, views, wrap).
+# to_bfloat16 / from_bfloat16 convert from and to float arrays.
+bfloat16 = np.dtype([("bits", "<u2")])
+
+_DT = {np.dtype(np.float32): _lib.WG_F32, np.dtype(np.float16): _lib.WG_F16, bfloat16: _lib.WG_BF16}
 
 
 def wg_dtype(dtype) -> int:
     try:
         return _DT[np.dtype(dtype)]
     except KeyError:
-        raise TypeError(f"element type {dtype} is not supported by the dense kernels (f32, f16)") from None
+        raise TypeError(f"element type {dtype} is not supported by the dense kernels (f32 / f16 / bf16: numpy.float32, numpy.float16, wgmath_amd.bfloat16)") from None
+
+
+def to_bfloat16(values) -> np.ndarray:
+    """float array -> array of `bfloat16` of the same shape: ONE round-to-nearest-even from float32 (the kernels' rounding: ties go to the even neighbour, a finite
+    value past the largest bf16 becomes Inf, subnormals are kept); a NaN stays a NaN (quiet, sign and high payload bits kept). Input that is not float32 is
+    converted to float32 first."""
+    u = np.ascontiguousarray(values, dtype=np.float32).view(np.uint32)
+    rounded = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)  # (no wrap: the largest non-NaN pattern is 0xFF800000)
+    nan = (u & np.uint32(0x7FFFFFFF)) > np.uint32(0x7F800000)
+    bits = np.where(nan, (u >> np.uint32(16)) | np.uint32(0x0040), rounded).astype(np.uint16)
+    return bits.view(bfloat16)
+
+
+def from_bfloat16(values) -> np.ndarray:
+    """array of `bfloat16` (or of its uint16 bit patterns) -> float32, exactly (the 16 bits become the high half)."""
+    arr = np.ascontiguousarray(values)
+    if arr.dtype != bfloat16 and arr.dtype != np.dtype(np.uint16):
+        raise TypeError(f"from_bfloat16 takes wgmath_amd.bfloat16 (or uint16 bit patterns), not {arr.dtype}")
+    return (arr.view(np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
 
 class BufferUsages(enum.IntFlag):
@@ -444,6 +468,8 @@ class TensorBuilder:
     def build_init(self, device: Device, data, dtype=None) -> "GpuTensor":
         """tensor.rs:175-186: asserts data.len() >= len, uploads the first `len` elements synchronously."""
         dt = np.dtype(dtype if dtype is not None else getattr(data, "dtype", np.float32))
+        if dt == bfloat16 and getattr(data, "dtype", None) != bfloat16:  # floats for a bf16 tensor: rounded here (NumPy cannot cast to the record type)
+            data = to_bfloat16(data)
         flat = _flat_col_major(data, dt)
         n = self.len()
         assert flat.size >= n, (
