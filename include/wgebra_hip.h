@@ -36,7 +36,7 @@ extern "C" {
 #endif
 
 #define WGEBRA_HIP_ABI_VERSION 5 /* 5: wg_debug_take_path; and the round-6 additions that came without a bump: wg_copy_view, wg_timestamps_reserve,
-                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE; and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
+                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE, wg_debug_gemm16_plan (an added diagnostic symbol with its two structs); and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
                                     that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
@@ -239,6 +239,56 @@ int wg_ctx_set_tuning(wg_ctx *ctx, wg_tuning key, int value);
 int wg_ctx_f16_balance_info(const wg_ctx *ctx, double *rel8, int *valid, uint32_t *updates, uint32_t *balanced_launches);
 int wg_debug_f16_balance_plan(const double *rel8, uint32_t tiles, uint32_t stages, int forced, uint32_t *units, uint32_t capacity, uint32_t *nunits,
                               uint32_t *nworkgroups);
+/* Diagnostics / tests (no context, no device): which leaf of the 16-bit Gemm launcher (f16 and bf16 share it) a call would take and with what.
+ * The launcher itself is "fill a wg_gemm16_query, ask the planner, do what the wg_gemm16_plan says"; this entry point asks the same planner.
+ * Everything a choice depends on is in the query; nothing in it needs a device. */
+typedef struct wg_gemm16_query {
+    uint32_t trans, M, N, K, nmats;          /* out (M x N) = op(m1) (M x K) * m2 (K x N); trans: m1 stored K x M */
+    uint32_t lda, ldb, ldc;                  /* leading dimensions of m1, m2 and out (elements) */
+    uint64_t a_batch, b_batch, c_batch;      /* matrix strides (elements) */
+    uint32_t a_addr, b_addr, c_addr;         /* the low 4 bits of the three base addresses (bytes) */
+    float alpha, beta;
+    uint32_t panels;                         /* the one-launch N-panel form (wg_gemm_sharded_panels): the widths follow */
+    uint32_t panel_cols, panel_n_main, panel_n_tail, panel_tail_cols[8];
+    uint32_t cus;                            /* compute units of the context's stream */
+    int32_t tile, sched, cont, balance;      /* WG_TUNE_F16_TILE, _SCHED, _CONT, _BALANCE */
+    uint32_t uneven_xcds;                    /* a CU-masked stream whose missing CUs all come from one XCD */
+    uint32_t recording;                      /* the call is being recorded into a command buffer */
+    uint32_t bal_valid;                      /* the context has measured per-XCD rates (wg_ctx_f16_balance_info) */
+    uint32_t padded;                         /* the inner call of a padded call: it must not pad again */
+} wg_gemm16_query;
+typedef enum wg_gemm16_leaf {
+    WG_GEMM16_SKINNY = 0,      /* few-column streaming kernel (GemmTr, N <= 16) */
+    WG_GEMM16_T256X128 = 1,    /* 256 x 128 tiles, two workgroups per CU */
+    WG_GEMM16_T128 = 2,        /* 128 x 128 tiles (+ split-K slabs and their reduce) */
+    WG_GEMM16_M16 = 3,         /* 256 x 256 tiles: per-tile launch (static map, tile queues or calibrated shares) or the continuous walk, + cut-up tail, + split-K */
+    WG_GEMM16_PAD = 4,         /* zero-padded copies of what does not qualify, then the same call on those */
+    WG_GEMM16_GENERIC = 5,     /* the generic fallback kernel */
+    WG_GEMM16_UNSUPPORTED = 6  /* no launch: the call returns `status` (with `message`, if there is one; WG_OK for an empty product) */
+} wg_gemm16_leaf;
+typedef struct wg_gemm16_plan {
+    uint32_t leaf;                           /* wg_gemm16_leaf */
+    uint32_t tiles_m, tiles_n;               /* tiles of the leaf's kernel (skinny: row blocks x 1) */
+    uint32_t nsplit, k_per_split;            /* K cut (1, K: none); every split but the last covers k_per_split, the last one the rest */
+    uint32_t c_stream, a_nt;                 /* result stored past the caches; op(A) read with the non-temporal hint */
+    uint64_t workspace_bytes;                /* split-K slabs or tail partials (the context's workspace) / the padded copies (its padding workspace) */
+    /* WG_GEMM16_M16: the launch of the whole tiles [0, tiles - tail), then the tail */
+    uint32_t cont;                           /* the continuous tile walk (one workgroup per CU) */
+    uint32_t queues;                         /* per-tile launch taking its tiles from the per-XCD queues */
+    uint32_t nwg;                            /* workgroups of that launch (per matrix and split; calibrated shares: decided from the measured rates) */
+    uint32_t bal_eligible, bal_calib, bal_wanted; /* calibrated shares: the shape allows them; this launch feeds the rate measurement; a plan is asked for */
+    uint32_t tail, tail_split, tail_kps;     /* tail tiles cut along K: how many (0: none), their splits and k per split */
+    /* WG_GEMM16_PAD */
+    uint32_t Mp, Kp, a_ok, b_ok, c_ok;       /* padded sizes; which of op(A), B and the output are used as they are */
+    uint32_t c_seed;                         /* the padded output starts as a copy of the old one (beta != 0) */
+    /* WG_GEMM16_UNSUPPORTED */
+    int32_t status;
+    char message[128];
+} wg_gemm16_plan;
+/* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path, element prefix "f16" or "bf16"), the
+ * slab reduce of a K cut included; for a padded call the pad tag followed by the inner call's tags. inner (may be NULL): the query of that inner call
+ * (pad plans only; else a copy of `query`). Calibrated shares are planned from flat rates (the forced pattern, WG_TUNE_F16_BALANCE = 1, ignores them). */
+int wg_debug_gemm16_plan(const wg_gemm16_query *query, const char *prefix, wg_gemm16_plan *plan, char *tags, size_t cap, wg_gemm16_query *inner);
 int wg_ctx_get_tuning(const wg_ctx *ctx, wg_tuning key, int *value);
 
 /* Pre-size the context's scratch (GEMV split-K partials) so that no operator allocates while recording. An operator that would

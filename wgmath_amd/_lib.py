@@ -30,6 +30,30 @@ class ViewShapeC(ctypes.Structure):
 assert ctypes.sizeof(ViewShapeC) == 24
 
 
+class Gemm16QueryC(ctypes.Structure):
+    """wg_gemm16_query: everything the 16-bit Gemm launcher's choice of kernels depends on (wg_debug_gemm16_plan)."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("trans", "M", "N", "K", "nmats", "lda", "ldb", "ldc")]
+                + [(n, ctypes.c_uint64) for n in ("a_batch", "b_batch", "c_batch")]
+                + [(n, ctypes.c_uint32) for n in ("a_addr", "b_addr", "c_addr")]
+                + [("alpha", ctypes.c_float), ("beta", ctypes.c_float)]
+                + [(n, ctypes.c_uint32) for n in ("panels", "panel_cols", "panel_n_main", "panel_n_tail")]
+                + [("panel_tail_cols", ctypes.c_uint32 * 8), ("cus", ctypes.c_uint32)]
+                + [(n, ctypes.c_int32) for n in ("tile", "sched", "cont", "balance")]
+                + [(n, ctypes.c_uint32) for n in ("uneven_xcds", "recording", "bal_valid", "padded")])
+
+
+GEMM16_LEAVES = ("skinny", "t256x128", "t128", "m16", "pad", "generic", "unsupported")  # wg_gemm16_leaf
+
+
+class Gemm16PlanC(ctypes.Structure):
+    """wg_gemm16_plan: the leaf (index into GEMM16_LEAVES) and what it is launched with."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("leaf", "tiles_m", "tiles_n", "nsplit", "k_per_split", "c_stream", "a_nt")]
+                + [("workspace_bytes", ctypes.c_uint64)]
+                + [(n, ctypes.c_uint32) for n in ("cont", "queues", "nwg", "bal_eligible", "bal_calib", "bal_wanted", "tail", "tail_split", "tail_kps",
+                                                   "Mp", "Kp", "a_ok", "b_ok", "c_ok", "c_seed")]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
+
+
 class WgError(RuntimeError):
     """A non-OK wg_status.  `.status` is the code, the message is wg_last_error_string()."""
 
@@ -87,6 +111,7 @@ def _load() -> ctypes.CDLL:
         "wg_ctx_mem_info": (ci, [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]),
         "wg_ctx_reserve_workspace": (ci, [vp, sz]),
         "wg_debug_f16_balance_plan": (ci, [ctypes.POINTER(ctypes.c_double), u32, u32, ci, ctypes.POINTER(u32), u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "wg_debug_gemm16_plan": (ci, [ctypes.POINTER(Gemm16QueryC), cp, ctypes.POINTER(Gemm16PlanC), cp, sz, ctypes.POINTER(Gemm16QueryC)]),
         "wg_ctx_f16_balance_info": (ci, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "wg_debug_take_path": (ci, [vp, cp, sz]),
         "wg_ctx_set_tuning": (ci, [vp, ci, ci]),

@@ -60,6 +60,9 @@ constexpr int HB_BYTES = BN * BKH * 2;
 constexpr int HSTAGE_BYTES = HA_BYTES + HB_BYTES; // 32 KiB
 constexpr int NSLOT = 5;                    // 5 x 32 KiB = all 160 KiB of LDS
 
+} // namespace WG16_NS (reopened below)
+
+namespace wg16 { // one definition for both element types: the planner unit (gemm16_plan.hip) is compiled once and fills the plan of either build
 // Calibrated shares across XCDs (gemm_f16.hip, "balance"). The XCDs of one chip differ by a few per cent in speed under the power cap,
 // hardware deals every XCD the same number of workgroups, and with a handful of tiles per CU whole tiles are too coarse to even that
 // out. So a FAST XCD ("taker") starts with one extra unit per CU -- the first `p` stages of K of a tile that belongs to a SLOW XCD
@@ -100,6 +103,11 @@ __host__ __device__ inline bool bal_decode(const BalancePlan &bp, uint32_t b, ui
         }
     return true;
 }
+} // namespace wg16
+
+namespace WG16_NS {
+using wg16::BalancePlan;
+using wg16::bal_decode;
 
 // N-panels with arrival counters (the M-sharded Gemm of comm.hip as ONE launch per step): the output is written panel by panel into the slots of a
 // staging cube [panel][rank][np x ldc] (col_stride = all ranks' rows of a column; slot_rows = the rows of the ranks in front of this one) -- or, with

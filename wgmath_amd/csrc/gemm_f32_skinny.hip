@@ -461,38 +461,20 @@ int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_
 #endif // !WG_GEMM16_BF16
 
 // f16 GemmTr with N <= 16 (f16 GemvTr with a few right-hand sides arrives here through wgk_gemm_f16): out = alpha * m1^T * m2 + beta * out, m1 stored K x M and m2
-// K x N, both k-contiguous. The caller (wgk_gemm_f16) has checked: K % 8 == 0, leading dimensions % 8 == 0, 16-byte aligned bases, 32-bit offsets in range.
+// K x N, both k-contiguous. The caller (wgk_gemm_f16, by its plan: gemm16_plan.hip) has checked: K % 8 == 0, leading dimensions % 8 == 0, 16-byte aligned bases,
+// 32-bit offsets in range; it chose the K cut (ns splits of kps), owns the f32 slabs (`part`, ns > 1) and reduces them.
 int WG16_SYM(wgk_gemm_, _skinny)(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_ext_t *out,
                         uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
-                        float alpha, float beta) {
-    const int cus = ctx->compute_units > 0 ? ctx->compute_units : 256;
+                        float alpha, float beta, uint32_t ns, uint32_t kps, float *part) {
     const uint32_t row_blocks = (M + 127u) / 128u;
-    const uint32_t max_split = (K + 255u) / 256u; // >= 256 k (4 stages) per workgroup
-    const uint64_t blocks = (uint64_t)row_blocks * nmats;
-    uint32_t ns = 1;
-    uint64_t best = ~0ull;
-    for (uint32_t c = 1; c <= max_split && (uint64_t)c * blocks <= 4ull * cus + blocks; ++c) { // the f32 launcher's plan at 64 k per stage
-        if ((uint64_t)c * M * N * nmats * 4u > (512ull << 20)) break;
-        const uint64_t rounds = (blocks * c + cus - 1) / cus;
-        const uint64_t cost = rounds * ((K + c - 1) / c + 256u);
-        if (cost < best) { best = cost; ns = c; }
-    }
-    uint32_t kps = (((K + ns - 1) / ns) + 63u) & ~63u;
-    ns = (K + kps - 1) / kps;
-    if (ns > 65535u || nmats > 65535u) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: too many splits or matrices for the skinny path");
-    void *ws = nullptr;
-    if (ns > 1)
-        if (int rc = wg_ctx_workspace(ctx, (size_t)ns * M * N * nmats * sizeof(float), &ws)) return rc;
     SkinnyArgs g;
     g.c = (float *)out; g.ldc = out_ld; g.c_batch = out_batch; g.alpha = alpha; g.beta = beta; g.crs = 1;
     g.a = (const float *)m1.ptr; g.lda = m1.ld; g.a_batch = m1.batch;
     g.b = (const float *)m2.ptr; g.ldb = m2.ld; g.b_batch = m2.batch;
-    g.part = (float *)ws; g.M = M; g.N = N; g.K = K; g.nsplit = ns; g.k_per_split = kps; g.npanels = 1;
+    g.part = part; g.M = M; g.N = N; g.K = K; g.nsplit = ns; g.k_per_split = kps; g.npanels = 1;
     g.rot = (uint64_t)(ns > 1 ? kps : K) * N * 2u <= (256u << 10) ? 1u : 0u;
     g.a_nt = (uint64_t)M * K * 2u >= (384ull << 20) ? 1u : 0u;
-    wg_path(ctx, WG16_TAG ".skinny/ns=%u", ns);
     hipLaunchKernelGGL((WG_SKINNY_KERNEL16<true, 1, false, true, sk_16>), dim3(row_blocks, ns, nmats), dim3(256), 0, ctx->stream, g);
     WG_HIP_TRY(hipGetLastError());
-    if (ns == 1) return WG_OK;
-    return wg_splitk_reduce(ctx, g.part, ns, M, N, nmats, WG16_DTYPE, out, out_ld, out_batch, alpha, beta);
+    return WG_OK;
 }

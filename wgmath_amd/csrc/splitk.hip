@@ -60,16 +60,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_strided_kernel(const float 
 
 } // namespace
 
-// How many K-splits to use (1 = none). `tiles` = output tiles x matrices, `slots` = workgroups the chip holds at once,
-// `k_units` = K / (kernel's K granule), `min_units` = fewest granules worth a workgroup's prologue/epilogue.
-uint32_t wg_splitk_plan(uint64_t tiles, uint32_t slots, uint32_t k_units, uint32_t min_units, uint64_t out_elems, uint64_t max_ws_bytes) {
-    if (tiles == 0 || tiles * 2 > slots) return 1; // at least half the chip is busy already
-    uint32_t s = (uint32_t)(slots / tiles);
-    const uint32_t by_k = k_units / min_units;
-    if (s > by_k) s = by_k;
-    while (s > 1 && (uint64_t)s * out_elems * 4u > max_ws_bytes) --s;
-    return s < 2 ? 1 : s;
-}
+// (wg_splitk_plan, how many K-splits to use: host arithmetic only, in gemm16_plan.hip with the rest of the 16-bit planner that calls it)
 
 int wg_splitk_reduce(wg_ctx *ctx, const float *part, uint32_t nsplit, uint32_t M, uint32_t N, uint32_t nmats, wg_dtype dtype, void *out,
                      uint32_t ldc, uint64_t c_batch, float alpha, float beta) {

@@ -200,11 +200,12 @@ int wgk_gemm_f32_mid(wg_ctx *ctx, bool trans, int bm, int bn, uint32_t M, uint32
 int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
                         wgk_mat m1, wgk_mat m2, float alpha, float beta, uint32_t out_row_stride = 1, bool m2_kmajor = false, uint32_t ns_force = 0);
 // f16 GemmTr with N <= 16 on the few-column streaming kernel (gemm_f32_skinny.hip, T = _Float16): HBM-bound, m1 read once
+// (launch only: the K cut -- ns splits of kps, f32 slabs in `part` -- is the caller's plan, gemm16_plan.hip, and so is the slabs' reduce)
 int wgk_gemm_f16_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, __half *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
-                        float alpha, float beta);
+                        float alpha, float beta, uint32_t ns, uint32_t kps, float *part);
 // bfloat16 (gemm_bf16_skinny.hip: the same kernel source compiled for the other 16-bit element type)
 int wgk_gemm_bf16_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg_bf16 *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
-                         float alpha, float beta);
+                         float alpha, float beta, uint32_t ns, uint32_t kps, float *part);
 // N-panels with arrival counters (comm.hip's one-launch-per-step sharded Gemm; gemm_f16_common.hpp PanelArgs): `out` is where the product's column 0
 // would sit if every panel were `cols` wide and the cube had one rank (i.e. panel 0's slot of this rank), leading dimension out_ld; panel p (first
 // column c0, np columns) lives at out + c0 * col_stride + slot_rows * (np - cols) ... see m16_tile. n_main panels of `cols` columns, then n_tail
@@ -244,7 +245,7 @@ int wgk_gemm_f32_nt(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nm
 int wg_gemm_f16_panels(wg_ctx *ctx, bool tr, void *out_panel0, uint32_t ldc, const wg_buf *m1, wg_view_shape m1_shape, const wg_buf *m2, wg_view_shape m2_shape,
                        const wgk_panels &panels);
 
-// split-K (splitk.hip)
+// split-K (the plan: gemm16_plan.hip; the reduce kernels: splitk.hip)
 uint32_t wg_splitk_plan(uint64_t tiles, uint32_t slots, uint32_t k_units, uint32_t min_units, uint64_t out_elems, uint64_t max_ws_bytes);
 // f32, beta = 0: out[z][r * row_stride + c * col_stride] = alpha * sum over splits (the transposed output of few-row products)
 int wg_splitk_reduce_strided(wg_ctx *ctx, const float *part, uint32_t nsplit, uint32_t M, uint32_t N, uint32_t nmats, float *out,
