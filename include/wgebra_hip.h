@@ -24,6 +24,21 @@
  *     or grid, kernel.rs:111-123,144) the call returns WG_OK and launches nothing.
  *   - Where the reference would read or write out of bounds (its shaders run with bounds checks disabled,
  *     wgcore utils.rs:11-19) the call returns WG_ERR_OUT_OF_BOUNDS / WG_ERR_PRECONDITION instead.
+ *   - OVERLAPPING OPERANDS ("the aliasing rule"; every operator's comment below refers to it). The footprint of a view is the set of elements
+ *     t*stride_mat + offset + i + j*stride it addresses -- for Reduce, OpAssign, Axpy and Gemv the elements the call really addresses (offset + i for a vector;
+ *     Gemv takes the column and matrix counts of `m` and `v` from `out`), the views the bounds checks use. A call whose WRITTEN footprint shares a byte with a
+ *     footprint it READS returns WG_ERR_ALIASED: nothing is launched, nothing is logged (wg_debug_take_path), no memory changes, a recording stays open and
+ *     usable; the message names the operator and both views ("Gemm: `out` overlaps `m1`"). The reference cannot get that far -- its kernels bind the output
+ *     read_write and the inputs read (gemm.wgsl:10-14, gemv.wgsl:10-14, op_assign.wgsl:8-10, reduce.wgsl:6-8), and wgpu refuses a dispatch that binds one
+ *     buffer both ways. Overlap is decided on ADDRESSES (device pointer + byte range), never on wg_buf identity: two handles over one allocation (wg_buf_wrap)
+ *     overlap like two views of one handle. Extension over wgpu, which tracks whole buffers: views of ONE buffer whose footprints are disjoint are legal --
+ *     views that touch, and views that interleave (an output that lives in the leading-dimension padding of an input).
+ *     The one exception (extension): wg_op_assign and wg_axpy take the IDENTICAL view -- same address, same length -- as `a` and `b` (`y` and `x`):
+ *     every element is loaded (both operands) before it is stored, by the lane that stores it, so `a += a`, `a *= a`, `y += alpha y` are well defined and
+ *     bit-equal to x (op) x. A partial overlap of `a` and `b` is refused.
+ *     Cost and the conservative bound: disjoint byte intervals are accepted after a few integer comparisons. Views whose intervals intersect are compared
+ *     exactly, column run by column run, while the two views have at most WG_VIEWS_OVERLAP_MAX_RUNS runs between them (a dense matrix or cube counts as one
+ *     run); beyond that the call is refused although the footprints might interleave without touching (the message then says "may overlap").
  */
 #ifndef WGEBRA_HIP_H
 #define WGEBRA_HIP_H
@@ -36,7 +51,8 @@ extern "C" {
 #endif
 
 #define WGEBRA_HIP_ABI_VERSION 5 /* 5: wg_debug_take_path; and the round-6 additions that came without a bump: wg_copy_view, wg_timestamps_reserve,
-                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE, wg_debug_gemm16_plan (an added diagnostic symbol with its two structs); and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
+                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE, wg_debug_gemm16_plan (an added diagnostic symbol with its two structs); WG_ERR_ALIASED = 9 (an appended status: calls that
+                                    return it used to launch kernels that raced on their own operands) with wg_debug_views_overlap; and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
                                     that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
@@ -53,8 +69,10 @@ typedef enum wg_status {
     WG_ERR_HIP = 5,           /* a HIP runtime call failed; message carries hipGetErrorString                 */
     WG_ERR_UNSUPPORTED = 6,   /* dtype/variant combination not implemented                                    */
     WG_ERR_NO_DEVICE = 7,     /* no gfx950 device visible (GpuInstance::new() -> Err, gpu.rs:24-58)           */
-    WG_ERR_WORKSPACE = 8      /* a context scratch region would have to grow while recording (allocation cannot be
+    WG_ERR_WORKSPACE = 8,     /* a context scratch region would have to grow while recording (allocation cannot be
                                  captured): run the call once eagerly, or wg_ctx_reserve_workspace, then record    */
+    WG_ERR_ALIASED = 9        /* the written view shares memory with a view the call reads (the aliasing rule above; the reference:
+                                 a wgpu validation panic). Nothing was launched                                     */
 } wg_status;
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -290,6 +308,14 @@ typedef struct wg_gemm16_plan {
  * (pad plans only; else a copy of `query`). Calibrated shares are planned from flat rates (the forced pattern, WG_TUNE_F16_BALANCE = 1, ignores them). */
 int wg_debug_gemm16_plan(const wg_gemm16_query *query, const char *prefix, wg_gemm16_plan *plan, char *tags, size_t cap, wg_gemm16_query *inner);
 int wg_ctx_get_tuning(const wg_ctx *ctx, wg_tuning key, int *value);
+/* Diagnostics / tests (no context, no device): the predicate behind WG_ERR_ALIASED. Returns 1 when the footprints of two views share a byte, 0 when they do not.
+ * byte_base_*: the byte address of element 0 of the buffer each view indexes (wg_buf_device_ptr; any integers do, only their difference matters); elem_size: bytes
+ * per element (both views). A view with a zero size overlaps nothing. Disjoint byte intervals are answered at once; intersecting intervals are decided exactly by
+ * walking column runs (one per column and matrix; columns that touch and matrices that touch are folded first, so dense views are one run) while the two views
+ * have at most WG_VIEWS_OVERLAP_MAX_RUNS runs between them; above that the answer is 1 whatever the truth. *exact (may be NULL) = 0 for such a conservative
+ * answer, 1 otherwise. The answer is never 0 for footprints that intersect. */
+#define WG_VIEWS_OVERLAP_MAX_RUNS 4096
+int wg_debug_views_overlap(wg_view_shape shape_a, uint64_t byte_base_a, wg_view_shape shape_b, uint64_t byte_base_b, uint32_t elem_size, int *exact);
 
 /* Pre-size the context's scratch (GEMV split-K partials) so that no operator allocates while recording. An operator that would
  * have to grow a scratch region inside a recording returns WG_ERR_WORKSPACE. Scratch regions that a live command buffer may
@@ -334,6 +360,7 @@ int wg_buf_fill_zero(wg_ctx *ctx, wg_buf *buf);
  *   *_FAST        : the reference requires K % 256 == 0 and reads out of bounds otherwise (gemm.wgsl:40,162);
  *                   here every K % 4 == 0 is accepted and all four variants run the same tuned kernel.
  * dtype WG_F16 (extension): f16 operands, f32 accumulation, result rounded once (RNE) to f16. WG_BF16 (extension): likewise on bfloat16 operands (wg_dtype).
+ *   ALIASED       : `out` shares a byte with `m1` or with `m2` (the aliasing rule, top of this file). `m1` and `m2` may overlap each other: both are only read.
  */
 int wg_gemm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype,
             wg_buf *out, wg_view_shape out_shape,
@@ -344,6 +371,7 @@ int wg_gemm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype,
  * Extension: BLAS-style update  out = alpha * op(m1) * m2 + beta * out.  Same views, checks and variants as
  * wg_gemm; beta == 0 never reads `out` (NaN/Inf there are overwritten, like wg_gemm), and (alpha, beta) = (1, 0) is
  * bit-identical to wg_gemm. alpha, beta are f32 for every dtype; f16 and bf16: alpha*acc + beta*c is formed in f32 and rounded once.
+ * ALIASED: `out` overlapping `m1` or `m2` (the aliasing rule) -- reading `out` itself for beta != 0 is the update, not an alias.
  */
 int wg_gemm_ex(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, float alpha, float beta,
                wg_buf *out, wg_view_shape out_shape,
@@ -361,6 +389,7 @@ int wg_gemm_ex(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, float alpha
  * dtype WG_F16 (extension): f16 elements, f32 accumulation, one rounding at the store -- the same HBM-bound kernels. WG_BF16 (extension): likewise on bfloat16 elements.
  * Several right-hand sides: one pass over the matrix for all of them; from 9 on -- and from 3 on when the matrix is past the launch-bound
  * sizes -- that pass runs on the Gemm kernels (same contract: f32 accumulation, results within the Gemv tolerance, deterministic).
+ *   ALIASED       : `out` shares a byte with the part of `m` or of `v` the call addresses (the aliasing rule; e.g. `out` = a column of `m`).
  */
 int wg_gemv(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype,
             wg_buf *out, wg_view_shape out_shape,
@@ -376,6 +405,8 @@ int wg_gemv(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype,
  * column-major kernel with the operands swapped (no copy); WG_GEMM_TR needs m1 transposed in memory first (one HBM-bound
  * pass into a context-owned scratch buffer). wg_gemv_rm with several right-hand-side columns (ncols % 4 == 0, the row-major
  * vec4 precondition) runs as the row-major Gemm / GemmTr it is.
+ * ALIASED: as wg_gemm / wg_gemv (the aliasing rule; a row-major view covers the same elements as its column-major twin), whichever kernels the call would take --
+ * the GemmTr that first copies m1 into scratch refuses an `out` that overlaps `m1` like the one that reads m1 where it lies.
  */
 int wg_gemm_rm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype,
                wg_buf *out, wg_view_shape out_shape,
@@ -393,6 +424,7 @@ int wg_gemv_rm(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype,
  * value (0, 1, +3.4e38, -3.4e38).
  * dtype WG_F16 (extension): `value` and `result` are f16; elements are converted to f32 (exact), folded in the same order in f32,
  * and the result is rounded once (RNE) to f16. (wg_reduce_batched and wg_reduce_fast likewise.) WG_BF16 (extension): likewise on bfloat16 (widening is exact).
+ * ALIASED: the result element (result[0]) lies inside value[offset .. offset+size[0]) (the aliasing rule). A result directly before or behind the vector is legal.
  */
 int wg_reduce(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype,
               const wg_buf *value, wg_view_shape value_shape, wg_buf *result);
@@ -402,6 +434,7 @@ int wg_reduce(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype,
  * Launch-bound sizes (Gemv, rows * cols <= 4 Mi, rows >= 128) run as ONE kernel: the last workgroup to finish folds the product
  * vector in the reference order (reduce.wgsl:68-87); everything else is Gemv into a context-owned scratch vector, then Reduce, on the
  * same stream. Either way bit-identical to wg_gemv followed by wg_reduce; `m` is one matrix, `v` one vector.
+ * ALIASED: result[0] lies inside `m` or inside `v` (the aliasing rule). The product vector is context-owned scratch and aliases nothing of the caller's.
  */
 int wg_gemv_reduce(wg_ctx *ctx, wg_gemv_variant variant, wg_reduce_op op, wg_dtype dtype, wg_buf *result,
                    const wg_buf *m, wg_view_shape m_shape, const wg_buf *v, wg_view_shape v_shape);
@@ -410,7 +443,7 @@ int wg_gemv_reduce(wg_ctx *ctx, wg_gemv_variant variant, wg_reduce_op op, wg_dty
  * Extension: two-pass, multi-workgroup reduce of ONE long vector at HBM speed. Same arguments and
  * checks as wg_reduce, but NOT the reference's summation order (which serialises a vector onto one workgroup): Min/Max
  * are bit-identical to wg_reduce, Sum/Prod/SqNorm are re-associated -- deterministic (fixed chunking and tree, no
- * atomics) and within n * 2^-24 * sum|x| (sum x^2 for SqNorm) of the reference order.
+ * atomics) and within n * 2^-24 * sum|x| (sum x^2 for SqNorm) of the reference order. ALIASED: as wg_reduce.
  */
 int wg_reduce_fast(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype,
                    const wg_buf *value, wg_view_shape value_shape, wg_buf *result);
@@ -419,6 +452,7 @@ int wg_reduce_fast(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype,
  * Extension (BASELINE config 4): one launch for many vectors. Column c of matrix t of the
  * column-major view is reduced exactly as wg_reduce would reduce the vector view at
  * offset + c*stride + t*stride_mat; results[c + t*size[1]] (one element of `dtype` each).
+ * ALIASED: one of the size[1] * size[2] result elements lies inside the `values` view (the aliasing rule).
  */
 int wg_reduce_batched(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype,
                       const wg_buf *values, wg_view_shape values_shape, wg_buf *results);
@@ -427,6 +461,8 @@ int wg_reduce_batched(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype,
  * OpAssign::dispatch (wgebra op_assign.rs:71-95): a[i] = a[i] (op) b[i], i < a.size[0]; WG_OP_COPY: a[i] = b[i].
  * Scalar indexing offset+i (shape.wgsl:36-38). DIM_MISMATCH: a.size[0] != b.size[0] (op_assign.rs:82-86).
  * IEEE-correct + - * / : bit-identical to the reference's CPU check.
+ * ALIASED: `a` and `b` overlap partly (the aliasing rule). Extension: `b` may be the IDENTICAL view -- same address, same length: every lane loads its a[i] and
+ * b[i] before it stores a[i], so the result is x (op) x to the bit (a += a doubles, a /= a gives 1, and NaN where IEEE says so: 0 / 0, Inf / Inf).
  */
 int wg_op_assign(wg_ctx *ctx, wg_op_assign_variant op, wg_dtype dtype,
                  wg_buf *a, wg_view_shape a_shape, const wg_buf *b, wg_view_shape b_shape);
@@ -435,6 +471,7 @@ int wg_op_assign(wg_ctx *ctx, wg_op_assign_variant op, wg_dtype dtype,
  * Extension (the north-star's "Axpy" -- the reference has no such operator, only OpAssign):
  * y[i] = fma(alpha, x[i], y[i]), i < y.size[0], one rounding per element. alpha = +1 / -1 reproduce WG_OP_ADD / WG_OP_SUB
  * (as `y += x` / `y -= x`) bit for bit. Same indexing, errors and skips as wg_op_assign. f16 and bf16: computed in f32, rounded once.
+ * ALIASED: as wg_op_assign -- a partial overlap of `y` and `x` is refused, the identical view is allowed (y[i] = fma(alpha, y[i], y[i])).
  */
 int wg_axpy(wg_ctx *ctx, float alpha, wg_dtype dtype, wg_buf *y, wg_view_shape y_shape, const wg_buf *x, wg_view_shape x_shape);
 
@@ -443,7 +480,8 @@ int wg_axpy(wg_ctx *ctx, float alpha, wg_dtype dtype, wg_buf *y, wg_view_shape y
  * (dst.size[0] x dst.size[1] per matrix; rows / columns of `src` beyond dst's are dropped). Any offset, stride and length on either side --
  * 16-byte accesses with a byte shift whatever the alignment (transpose.hip). It is the pass wg_gemm* / wg_gemv* run for operands that are
  * not vec4-aligned; a caller that multiplies the same odd view many times makes the aligned copy ONCE with this and passes that instead.
- * DIM_MISMATCH: dst.size[2] != src.size[2]. Zero-sized views: skipped. The views must not overlap.
+ * DIM_MISMATCH: dst.size[2] != src.size[2]. Zero-sized views: skipped. ALIASED: `dst` shares a byte with `src` (the aliasing rule; no exception for identical
+ * views: a copy onto itself is refused like a copy shifted by one row).
  */
 int wg_copy_view(wg_ctx *ctx, wg_dtype dtype, wg_buf *dst, wg_view_shape dst_shape, const wg_buf *src, wg_view_shape src_shape);
 
@@ -530,7 +568,9 @@ int wg_cube_to_matrix(wg_ctx *ctx, wg_dtype dtype, const wg_buf *cube, wg_view_s
  * (M/P x K; WG_GEMM_TR*: stored K x M/P), `b` (K x N) is replicated. N is cut into panels of `panel_cols` columns (0 = default)
  * and panel i's exchange overlaps panel i+1's Gemm.
  * On return everything is enqueued: `out` is complete in context-stream order (WG_GATHER_NONE: this rank's rows only).
- * DIM_MISMATCH as Gemm (gemm.rs:91-95) with M = P * rows(a_rows).
+ * DIM_MISMATCH as Gemm (gemm.rs:91-95) with M = P * rows(a_rows). ALIASED: `out` shares a byte with `a_rows` or with `b` (the aliasing
+ * rule; checked once, in every gather mode, before anything is launched); the one-launch forms also refuse `a_rows` / `b` views that lie in the communicator's staging cube
+ * (wg_comm_stage_reserve hands that buffer out) where this rank's panels of the step are written ("Gemm: `out` overlaps `m1`" / "`m2`") -- operands elsewhere in the cube are legal.
  */
 int wg_gemm_sharded(wg_comm *comm, wg_gemm_variant variant, wg_dtype dtype, wg_gather_mode mode, uint32_t panel_cols,
                     wg_buf *out, wg_view_shape out_shape,

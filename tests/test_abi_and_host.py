@@ -22,7 +22,8 @@ def test_library_exports_every_declared_symbol_at_abi_5():
     assert not missing, f"include/wgebra_hip.h declares symbols the library does not export: {missing}"
     assert set(declared) == set(_lib.lib._wg_signatures), "the ctypes binding and the header disagree on the entry points"
     # 3: the SDMA rect-copy exchange engine is gone (gather mode 1, wg_comm_copy_engine, peer_out), + wg_comm_reported_size, wg_debug_clock_*, wg_debug_mfma_ceiling; 5: wg_debug_take_path
-    # (added since without a bump, as the round-6 additions were: wg_debug_gemm16_plan -- tests/test_gemm16_plan_host.py)
+    # (added since without a bump, as the round-6 additions were: wg_debug_gemm16_plan -- tests/test_gemm16_plan_host.py; wg_debug_views_overlap with the
+    # appended status WG_ERR_ALIASED -- tests/test_operand_overlap.py)
     hdr = open(_lib.HEADER_PATH).read()
     assert _lib.lib.wg_abi_version() == _lib.ABI_VERSION == 5 and f"#define WGEBRA_HIP_ABI_VERSION {_lib.ABI_VERSION} " in hdr
 
@@ -153,6 +154,17 @@ def test_enums_keep_reference_order():
                  "WG_REDUCE_MIN = 0, WG_REDUCE_MAX = 1, WG_REDUCE_SUM = 2, WG_REDUCE_PROD = 3, WG_REDUCE_SQNORM = 4",
                  "WG_OP_ADD = 0, WG_OP_SUB = 1, WG_OP_MUL = 2, WG_OP_DIV = 3, WG_OP_COPY = 4"):
         assert name in hdr
+    # wg_status: the header's values, the binding's constants and the exception each one raises (WG_ERR_ALIASED = 9 was appended: no earlier value moved)
+    import re
+    status = re.search(r"typedef enum wg_status \{(.*?)\} wg_status;", hdr, re.S).group(1)
+    values = {n: int(v) for n, v in re.findall(r"\b(WG_[A-Z_]+) = (\d+)", re.sub(r"/\*.*?\*/", "", status, flags=re.S))}
+    assert values == {"WG_OK": 0, "WG_ERR_DIM_MISMATCH": 1, "WG_ERR_PRECONDITION": 2, "WG_ERR_INVALID_ARG": 3, "WG_ERR_OUT_OF_BOUNDS": 4, "WG_ERR_HIP": 5,
+                      "WG_ERR_UNSUPPORTED": 6, "WG_ERR_NO_DEVICE": 7, "WG_ERR_WORKSPACE": 8, "WG_ERR_ALIASED": 9}
+    assert all(getattr(_lib, n) == v for n, v in values.items())
+    assert _lib._EXC == {_lib.WG_ERR_DIM_MISMATCH: wg.DimensionMismatch, _lib.WG_ERR_PRECONDITION: wg.PreconditionFailed, _lib.WG_ERR_NO_DEVICE: wg.NoDevice,
+                         _lib.WG_ERR_WORKSPACE: wg.WorkspaceMustGrow, _lib.WG_ERR_ALIASED: wg.AliasedOperands}
+    facade = open(os.path.join(ROOT, "include", "wgebra.hpp")).read()
+    assert "rc == WG_ERR_ALIASED) throw Panic(rc, msg);" in facade  # where wgpu's validation panics, the C++ mirror throws wgcore::Panic
 
 
 def test_reduce_eval_cpu_matches_reference_helper():

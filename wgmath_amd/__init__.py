@@ -4,7 +4,7 @@ The product is libwgebra_hip.so (hand-written HIP kernels + C ABI, sources in cs
 This package is the thin host-side mirror of the reference's wgcore/wgebra API used by the tests and the bench.
 Importing it loads the shared library and fails loudly if it is not built: there is no CPU or PyTorch fallback.
 """
-from ._lib import (LIB_PATH, DimensionMismatch, NoDevice, PreconditionFailed, WgError, WorkspaceMustGrow)  # noqa: F401
+from ._lib import (LIB_PATH, AliasedOperands, DimensionMismatch, NoDevice, PreconditionFailed, WgError, WorkspaceMustGrow)  # noqa: F401
 from .wgcore import (BufferUsages, CommandBuffer, CommandEncoder, ComputePass, Device, GpuCube, GpuInstance,  # noqa: F401
                      GpuBuffer, GpuMatrix, GpuScalar, GpuTensor, GpuTensorView, GpuTimestamps, ComputePassTimestampWrites, GpuVector, Queue, TensorBuilder,
                      ViewShape, ViewShapeBuffers, as_view, bfloat16, from_bfloat16, to_bfloat16)

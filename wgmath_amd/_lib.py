@@ -13,7 +13,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "wgebra_hip.h")
 
 # status codes (wg_status)
 WG_OK, WG_ERR_DIM_MISMATCH, WG_ERR_PRECONDITION, WG_ERR_INVALID_ARG, WG_ERR_OUT_OF_BOUNDS, WG_ERR_HIP, \
-    WG_ERR_UNSUPPORTED, WG_ERR_NO_DEVICE, WG_ERR_WORKSPACE = range(9)
+    WG_ERR_UNSUPPORTED, WG_ERR_NO_DEVICE, WG_ERR_WORKSPACE, WG_ERR_ALIASED = range(10)
+WG_VIEWS_OVERLAP_MAX_RUNS = 4096  # == the header's: above it wg_debug_views_overlap answers "overlaps" without deciding
 WG_GATHER_RCCL, WG_GATHER_NONE, WG_GATHER_PEER_STAGED = 0, 2, 3  # (1 was the SDMA rect-copy engine: removed in ABI 3)
 WG_COMM_ID_BYTES, WG_IPC_HANDLE_BYTES = 128, 96
 ABI_VERSION = 5  # == WGEBRA_HIP_ABI_VERSION (checked when the library is loaded, and against the header by tests/test_abi_and_host.py)
@@ -78,6 +79,12 @@ class WorkspaceMustGrow(WgError):
     """A context scratch region would have to grow inside a recording (WG_ERR_WORKSPACE): run the call once eagerly first."""
 
 
+class AliasedOperands(WgError):
+    """The written view of a call shares memory with a view the call reads (WG_ERR_ALIASED): nothing was launched. The reference gets a wgpu validation panic
+    for binding one buffer read_write and read; here views of one buffer are legal as long as their footprints are disjoint, and OpAssign / Axpy take the
+    identical view on both sides (include/wgebra_hip.h, the aliasing rule)."""
+
+
 def declared_symbols(header_path: str = HEADER_PATH) -> list[str]:
     """Every function the public header declares (used by the ABI-completeness test)."""
     text = open(header_path).read()
@@ -113,6 +120,7 @@ def _load() -> ctypes.CDLL:
         "wg_debug_f16_balance_plan": (ci, [ctypes.POINTER(ctypes.c_double), u32, u32, ci, ctypes.POINTER(u32), u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "wg_debug_gemm16_plan": (ci, [ctypes.POINTER(Gemm16QueryC), cp, ctypes.POINTER(Gemm16PlanC), cp, sz, ctypes.POINTER(Gemm16QueryC)]),
         "wg_ctx_f16_balance_info": (ci, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "wg_debug_views_overlap": (ci, [S, u64, S, u64, u32, ctypes.POINTER(ci)]),
         "wg_debug_take_path": (ci, [vp, cp, sz]),
         "wg_ctx_set_tuning": (ci, [vp, ci, ci]),
         "wg_ctx_get_tuning": (ci, [vp, ci, ctypes.POINTER(ci)]),
@@ -216,7 +224,8 @@ def assert_single_hip_runtime() -> None:
 
 lib = _load()
 
-_EXC = {WG_ERR_DIM_MISMATCH: DimensionMismatch, WG_ERR_PRECONDITION: PreconditionFailed, WG_ERR_NO_DEVICE: NoDevice, WG_ERR_WORKSPACE: WorkspaceMustGrow}
+_EXC = {WG_ERR_DIM_MISMATCH: DimensionMismatch, WG_ERR_PRECONDITION: PreconditionFailed, WG_ERR_NO_DEVICE: NoDevice, WG_ERR_WORKSPACE: WorkspaceMustGrow,
+        WG_ERR_ALIASED: AliasedOperands}
 
 
 def check(status: int) -> None:

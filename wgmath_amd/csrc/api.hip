@@ -1,7 +1,9 @@
 // Operator front-end of the C ABI: the host-side half of Gemm/Gemv/Reduce/OpAssign::dispatch.
 // Mirrors, check for check, wgebra gemm.rs:75-126, gemv.rs:74-136, reduce.rs:100-113, op_assign.rs:79-94 and the
-// silent-skip rules of wgcore kernel.rs:111-123,144; adds the bounds/alignment checks the reference leaves to UB.
+// silent-skip rules of wgcore kernel.rs:111-123,144; adds the bounds/alignment checks the reference leaves to UB, and the check wgpu makes before the reference's
+// kernels ever run: a view that is written must not share memory with a view the same call reads (check_alias; the rule: include/wgebra_hip.h).
 #include "wg_internal.hpp"
+#include "views_overlap.hpp"
 
 namespace {
 
@@ -23,6 +25,23 @@ int check_bounds(const char *op, const char *name, const View &v, const wg_buf *
                             (unsigned long long)need, (unsigned long long)have);
     return WG_OK;
 }
+
+// The aliasing rule (include/wgebra_hip.h): the written view `w` of a call must not share a byte with a view `r` it reads. Asked after the bounds checks and before
+// anything is launched or logged, on the views the call really addresses (the ones check_bounds gets) and on addresses -- base_*: element 0 of each view's buffer --,
+// not on wg_buf identity. The predicate is views_overlap.hip: disjoint byte intervals cost a few comparisons.
+inline wg_view_shape shape_of(const View &v) {
+    wg_view_shape s;
+    s.size[0] = v.rows; s.size[1] = v.cols; s.size[2] = v.mats; s.stride = v.stride; s.stride_mat = v.stride_mat; s.offset = v.offset;
+    return s;
+}
+int check_alias(const char *op, wg_dtype dt, const char *wname, const View &w, const void *base_w, const char *rname, const View &r, const void *base_r) {
+    int exact = 1;
+    if (!wg_views_overlap(shape_of(w), (uint64_t)(uintptr_t)base_w, shape_of(r), (uint64_t)(uintptr_t)base_r, (uint32_t)wg_dtype_size(dt), &exact)) return WG_OK;
+    if (exact) return wg_set_error(WG_ERR_ALIASED, "%s: `%s` overlaps `%s` (the written view shares memory with a view the call reads)", op, wname, rname);
+    return wg_set_error(WG_ERR_ALIASED, "%s: `%s` may overlap `%s` (their byte ranges intersect and they have more than %d column runs between them: not decided exactly)", op,
+                        wname, rname, WG_VIEWS_OVERLAP_MAX_RUNS);
+}
+inline View one_element() { return View{ 1, 1, 1, 1, 1, 0 }; } // the result scalar of a Reduce: element 0 of its buffer
 
 // The reference's kernels bind every buffer as array<vec4<f32>> (gemm.wgsl:9-14, gemv.wgsl:9-14) and convert shapes with
 // with_vec4_elts (shape.wgsl:64-66): rows, stride, stride_mat and offset must be multiples of 4 for that to address
@@ -140,6 +159,10 @@ int gemv_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, wg_buf *out, const View &o
 
 } // namespace
 
+int wg_check_alias(const char *op, wg_dtype dtype, const char *wname, wg_view_shape w, const void *base_w, const char *rname, wg_view_shape r, const void *base_r) {
+    return check_alias(op, dtype, wname, mk(w), base_w, rname, mk(r), base_r);
+}
+
 int wg_gemm_f16_panels(wg_ctx *ctx, bool tr, void *out_panel0, uint32_t ldc, const wg_buf *m1, wg_view_shape m1_shape, const wg_buf *m2, wg_view_shape m2_shape,
                        const wgk_panels &panels) {
     const View a = mk(m1_shape), b = mk(m2_shape);
@@ -148,6 +171,20 @@ int wg_gemm_f16_panels(wg_ctx *ctx, bool tr, void *out_panel0, uint32_t ldc, con
     if (!vec4_ok(a) || !vec4_ok(b) || m_rows % 4 || m_cols % 4 || b.cols % 4) return WG_ERR_UNSUPPORTED;
     if (int rc = check_bounds("Gemm", "m1", a, m1, WG_F16)) return rc;
     if (int rc = check_bounds("Gemm", "m2", b, m2, WG_F16)) return rc;
+    // the panels this launch writes (wgk_panels: panel p, np columns from column c0 on, is the dense m_rows x np block at out_panel0 + c0 * col_stride + slot_rows * (np - cols))
+    // against the two operands: the communicator's staging cube is a buffer the caller can get hold of (wg_comm_stage_reserve)
+    {
+        uint64_t c0 = 0;
+        for (uint32_t p = 0; p < panels.n_main + panels.n_tail; ++p) {
+            const uint32_t np = p < panels.n_main ? panels.cols : panels.tail_cols[p - panels.n_main];
+            const int64_t first = (int64_t)(c0 * panels.col_stride) + (int64_t)panels.slot_rows * ((int64_t)np - (int64_t)panels.cols);
+            const char *base = (const char *)out_panel0 + first * (int64_t)wg_dtype_size(WG_F16);
+            const View o = { m_rows, np, 1, ldc, 0, 0 };
+            if (int rc = check_alias("Gemm", WG_F16, "out", o, base, "m1", a, m1->ptr)) return rc;
+            if (int rc = check_alias("Gemm", WG_F16, "out", o, base, "m2", b, m2->ptr)) return rc;
+            c0 += np;
+        }
+    }
     const wgk_mat A = { elem_ptr(m1, a.offset, WG_F16), a.stride, a.stride_mat }, B = { elem_ptr(m2, b.offset, WG_F16), b.stride, b.stride_mat };
     return wgk_gemm_f16(ctx, tr, m_rows, b.cols, m_cols, 1, (__half *)out_panel0, ldc, 0, A, B, 1.f, 0.f, &panels);
 }
@@ -181,6 +218,8 @@ int wg_gemm_ex(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, float alpha
     if (int rc = check_bounds("Gemm", "out", o, out, dtype)) return rc;
     if (int rc = check_bounds("Gemm", "m1", a, m1, dtype)) return rc;
     if (int rc = check_bounds("Gemm", "m2", b, m2, dtype)) return rc;
+    if (int rc = check_alias("Gemm", dtype, "out", o, out->ptr, "m1", a, m1->ptr)) return rc;
+    if (int rc = check_alias("Gemm", dtype, "out", o, out->ptr, "m2", b, m2->ptr)) return rc;
 
     WG_HIP_TRY(hipSetDevice(ctx->device));
     // lengths the kernels' 4 x 4 blocks do not take (gemm.wgsl:87,94): zero-padded copies of the operands that carry them
@@ -231,6 +270,8 @@ int wg_gemv(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype, wg_buf *out, w
     if (int rc = check_bounds("Gemv", "out", o, out, dtype)) return rc;
     if (int rc = check_bounds("Gemv", "m", m_eff, m, dtype)) return rc;
     if (int rc = check_bounds("Gemv", "v", v_eff, v, dtype)) return rc;
+    if (int rc = check_alias("Gemv", dtype, "out", o, out->ptr, "m", m_eff, m->ptr)) return rc;
+    if (int rc = check_alias("Gemv", dtype, "out", o, out->ptr, "v", v_eff, v->ptr)) return rc;
 
     WG_HIP_TRY(hipSetDevice(ctx->device));
     // views / sizes the vec4 kernels cannot address as they are (shape.wgsl:64-66; gemv.wgsl:73,76): the any-alignment kernels (a matrix that is off), or copies of the vectors
@@ -250,6 +291,7 @@ int wg_reduce(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype, const wg_buf *value,
     // reduce.wgsl:71-72: input[offset + i], i < nrows; stride / ncols / nmats are ignored
     const View vec = { value_shape.size[0], 1, 1, 1, 1, value_shape.offset };
     if (int rc = check_bounds("Reduce", "value", vec, value, dtype)) return rc;
+    if (int rc = check_alias("Reduce", dtype, "result", one_element(), result->ptr, "value", vec, value->ptr)) return rc;
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_reduce(ctx, (int)op, dtype, elem_ptr(value, vec.offset, dtype), vec.rows, 1, 1, 0, 0, result->ptr);
 }
@@ -262,6 +304,7 @@ int wg_reduce_fast(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype, const wg_buf *v
     if (result->bytes < wg_dtype_size(dtype)) return wg_set_error(WG_ERR_OUT_OF_BOUNDS, "Reduce: result buffer smaller than one element");
     const View vec = { value_shape.size[0], 1, 1, 1, 1, value_shape.offset };
     if (int rc = check_bounds("Reduce", "value", vec, value, dtype)) return rc;
+    if (int rc = check_alias("Reduce", dtype, "result", one_element(), result->ptr, "value", vec, value->ptr)) return rc;
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_reduce_fast(ctx, (int)op, dtype, elem_ptr(value, vec.offset, dtype), vec.rows, result->ptr);
 }
@@ -280,6 +323,15 @@ int wg_gemv_reduce(wg_ctx *ctx, wg_gemv_variant variant, wg_reduce_op op, wg_dty
     if (vv.cols != 1 || vv.mats != 1 || mm.mats != 1)
         return wg_set_error(WG_ERR_UNSUPPORTED, "gemv_reduce: one matrix and one vector only");
     const uint32_t out_rows = tr ? mm.cols : mm.rows;
+    // The result scalar against the matrix and the vector -- before anything is allocated, launched or logged. (The two launches below see `result` only next to the
+    // context's scratch vector, which aliases nothing of the caller's.) For a call wg_gemv would neither refuse for its dimensions nor skip: its bounds checks first.
+    if ((tr ? mm.rows : mm.cols) == vv.rows && out_rows != 0 && m->bytes != 0 && v->bytes != 0) {
+        const View m_eff = { mm.rows, mm.cols, 1, mm.stride, mm.stride_mat, mm.offset }, v_eff = { vv.rows, 1, 1, vv.stride, vv.stride_mat, vv.offset };
+        if (int rc = check_bounds("Gemv", "m", m_eff, m, dtype)) return rc;
+        if (int rc = check_bounds("Gemv", "v", v_eff, v, dtype)) return rc;
+        if (int rc = check_alias("GemvReduce", dtype, "result", one_element(), result->ptr, "m", m_eff, m->ptr)) return rc;
+        if (int rc = check_alias("GemvReduce", dtype, "result", one_element(), result->ptr, "v", v_eff, v->ptr)) return rc;
+    }
     void *ws = nullptr;
     if (int rc = wg_ctx_tr_workspace(ctx, (size_t)(out_rows ? out_rows : 4) * sizeof(float), &ws)) return rc;
     // Launch-bound sizes (the single-kernel Gemv family): ONE launch -- the last workgroup to finish folds y in the reference order
@@ -321,6 +373,8 @@ int wg_reduce_batched(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype, const wg_buf
                             results->bytes / wg_dtype_size(dtype), (unsigned long long)nvec);
     if (values->bytes == 0 && v.rows != 0) return WG_OK;
     if (int rc = check_bounds("Reduce", "values", v, values, dtype)) return rc;
+    // results[c + t * cols]: cols x mats elements back to back from element 0 of their buffer
+    if (int rc = check_alias("Reduce", dtype, "results", View{ v.cols, v.mats, 1, v.cols, 0, 0 }, results->ptr, "values", v, values->ptr)) return rc;
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_reduce(ctx, (int)op, dtype, elem_ptr(values, v.offset, dtype), v.rows, v.cols, v.mats, v.stride, v.stride_mat,
                       results->ptr);
@@ -342,6 +396,10 @@ int wg_op_assign(wg_ctx *ctx, wg_op_assign_variant op, wg_dtype dtype, wg_buf *a
     const View va = { n, 1, 1, 1, 1, a_shape.offset }, vb = { n, 1, 1, 1, 1, b_shape.offset };
     if (int rc = check_bounds("OpAssign", "a", va, a, dtype)) return rc;
     if (int rc = check_bounds("OpAssign", "b", vb, b, dtype)) return rc;
+    // the identical view as `a` and `b` (same address; the lengths are equal) is defined: every lane of op_assign.hip's kernels loads its a[i] and b[i] before it
+    // stores a[i], in the 16-byte body and in the scalar head and tail alike. Any other overlap is a race between lanes.
+    if (elem_ptr(a, va.offset, dtype) != elem_ptr(b, vb.offset, dtype))
+        if (int rc = check_alias("OpAssign", dtype, "a", va, a->ptr, "b", vb, b->ptr)) return rc;
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_op_assign(ctx, (int)op, dtype, (void *)elem_ptr(a, va.offset, dtype), elem_ptr(b, vb.offset, dtype), n);
 }
@@ -357,6 +415,8 @@ int wg_axpy(wg_ctx *ctx, float alpha, wg_dtype dtype, wg_buf *y, wg_view_shape y
     const View vy = { n, 1, 1, 1, 1, y_shape.offset }, vx = { n, 1, 1, 1, 1, x_shape.offset };
     if (int rc = check_bounds("Axpy", "y", vy, y, dtype)) return rc;
     if (int rc = check_bounds("Axpy", "x", vx, x, dtype)) return rc;
+    if (elem_ptr(y, vy.offset, dtype) != elem_ptr(x, vx.offset, dtype)) // (the identical view: defined, as in wg_op_assign)
+        if (int rc = check_alias("Axpy", dtype, "y", vy, y->ptr, "x", vx, x->ptr)) return rc;
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_op_assign(ctx, 5 /* axpy */, dtype, (void *)elem_ptr(y, vy.offset, dtype), elem_ptr(x, vx.offset, dtype), n, alpha);
 }
@@ -371,6 +431,8 @@ int wg_copy_view(wg_ctx *ctx, wg_dtype dtype, wg_buf *dst, wg_view_shape dst_sha
     const bool empty_src = src->bytes == 0 || s.rows == 0 || s.cols == 0;
     if (!empty_src)
         if (int rc = check_bounds("CopyView", "src", s, src, dtype)) return rc;
+    if (!empty_src)
+        if (int rc = check_alias("CopyView", dtype, "dst", d, dst->ptr, "src", s, src->ptr)) return rc;
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_stage_copy(ctx, dtype, (void *)elem_ptr(dst, d.offset, dtype), d.stride, d.stride_mat, d.rows, d.cols, empty_src ? dst->ptr : elem_ptr(src, s.offset, dtype),
                           s.stride, s.stride_mat, empty_src ? 0u : s.rows, empty_src ? 0u : s.cols, d.mats);
@@ -393,6 +455,19 @@ static wg_view_shape relabel(wg_view_shape s) {
     return s;
 }
 
+// The aliasing rule of a row-major product, under the caller's operator and operand names: a row-major view covers the same elements as its column-major twin. For a
+// call that is not skipped: bounds first, as everywhere.
+static int check_alias_rm(const char *op, wg_dtype dtype, const wg_buf *out, wg_view_shape out_shape, const char *n1, const wg_buf *m1, wg_view_shape m1_shape, const char *n2,
+                          const wg_buf *m2, wg_view_shape m2_shape) {
+    const View o = mk(relabel(out_shape)), a = mk(relabel(m1_shape)), b = mk(relabel(m2_shape));
+    if (out->bytes == 0 || m1->bytes == 0 || m2->bytes == 0 || o.rows == 0 || o.cols == 0 || o.mats == 0) return WG_OK;
+    if (int rc = check_bounds(op, "out", o, out, dtype)) return rc;
+    if (int rc = check_bounds(op, n1, a, m1, dtype)) return rc;
+    if (int rc = check_bounds(op, n2, b, m2, dtype)) return rc;
+    if (int rc = check_alias(op, dtype, "out", o, out->ptr, n1, a, m1->ptr)) return rc;
+    return check_alias(op, dtype, "out", o, out->ptr, n2, b, m2->ptr);
+}
+
 int wg_gemm_rm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, wg_buf *out, wg_view_shape out_shape, const wg_buf *m1,
                wg_view_shape m1_shape, const wg_buf *m2, wg_view_shape m2_shape) {
     const wg_buf *bufs[3] = { out, m1, m2 };
@@ -405,6 +480,9 @@ int wg_gemm_rm(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, wg_buf *out
         return wg_set_error(WG_ERR_DIM_MISMATCH,
                             "Gemm: dimension mismatch. (out [%u,%u,%u], m1 [%u,%u,%u]%s, m2 [%u,%u,%u])", o.rows, o.cols, o.mats,
                             a.rows, a.cols, a.mats, tr ? "^T" : "", b.rows, b.cols, b.mats);
+    // The aliasing rule under this entry point's own operand names: the forwarded calls swap m1 and m2, and the GemmTr that copies m1 into scratch would never see
+    // `out` next to it.
+    if (int rc = check_alias_rm("Gemm", dtype, out, out_shape, "m1", m1, m1_shape, "m2", m2, m2_shape)) return rc;
     if (!tr) return wg_gemm_ex(ctx, WG_GEMM, dtype, 1.f, 0.f, out, relabel(out_shape), m2, relabel(m2_shape), m1, relabel(m1_shape));
 
     // m1 is K x M row-major == column-major M x K (ld = stride); the column-major Gemm needs it as K x M column-major
@@ -471,6 +549,7 @@ int wg_gemv_rm(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype, wg_buf *out
         ms.size[2] = o.mats;
         vs.size[1] = o.cols;
         vs.size[2] = o.mats;
+        if (int rc = check_alias_rm("Gemv", dtype, out, os, "m", m, ms, "v", v, vs)) return rc; // (the refusal names the call that was made, not the Gemm it becomes)
         return wg_gemm_rm(ctx, tr ? WG_GEMM_TR : WG_GEMM, dtype, out, os, m, ms, v, vs);
     }
     return wg_gemv(ctx, tr ? WG_GEMV : WG_GEMV_TR, dtype, out, out_shape, m, relabel(m_shape), v, v_shape);

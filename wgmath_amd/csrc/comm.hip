@@ -649,6 +649,13 @@ static int gemm_sharded_impl(wg_comm *c, wg_gemm_variant variant, wg_dtype dtype
     if (M == 0 || N == 0) return WG_OK;
     if (mg % 4 || N % 4) return wg_set_error(WG_ERR_PRECONDITION, "Gemm (sharded): the row block (%u rows) and N=%u must be multiples of 4 (vec4 views, shape.wgsl:64-66)", mg, N);
     if (mode == WG_GATHER_RCCL && P > 1 && !c->nccl) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm (sharded): WG_GATHER_RCCL needs a communicator created with a unique id");
+    // The aliasing rule for `out`, once, before any state of the communicator moves and before anything is launched: in the gathered modes the Gemms write the staging
+    // cube and the relayouts write `out`, panel by panel, so no later check would see `out` next to an operand (and WG_GATHER_NONE would refuse at the first panel that
+    // overlaps, after the launches of the panels before it).
+    if (a_rows->bytes != 0 && b->bytes != 0 && out->bytes != 0) {
+        if (int rc = wg_check_alias("Gemm (sharded)", dtype, "out", out_shape, out->ptr, "a_rows", a_shape, a_rows->ptr)) return rc;
+        if (int rc = wg_check_alias("Gemm (sharded)", dtype, "out", out_shape, out->ptr, "b", b_shape, b->ptr)) return rc;
+    }
     // ---- the panel plan: first column and width of every panel ----
     std::vector<uint32_t> pc0, pnp;
     {
@@ -793,6 +800,7 @@ static int gemm_sharded_impl(wg_comm *c, wg_gemm_variant variant, wg_dtype dtype
                 }
                 return WG_OK;
             }
+            if (rc1 == WG_ERR_ALIASED) --c->step; // (refused before any Gemm was launched: the step was not taken, the next call uses this parity's half)
             if (rc1 != WG_ERR_UNSUPPORTED) return rc1; // (unsupported: not that kind of product -- panel by panel below)
         }
         for (uint32_t p = 0; p < npanels; ++p) {
@@ -918,6 +926,7 @@ static int gemm_sharded_impl(wg_comm *c, wg_gemm_variant variant, wg_dtype dtype
             }
             return WG_OK;
         }
+        if (rc1 == WG_ERR_ALIASED) --c->step; // (refused before any Gemm was launched: the step was not taken)
         if (rc1 != WG_ERR_UNSUPPORTED) return rc1;
         if (int rc = run_pending(c)) return rc; // panel by panel below
     }

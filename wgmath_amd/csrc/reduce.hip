@@ -53,6 +53,16 @@ __device__ __forceinline__ float4 load4(const H *p, bool nt) {
     return make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
 }
 
+// The folded f32 value as an element of the result. For a 16-bit type the value is fenced first: without it hipcc fuses the LAST multiplication of a Prod with the
+// conversion (v_fma_mixlo_f16 a, b, +0), which rounds the exact product straight to 16 bits -- not the f32 product rounded once more, as the contract and the
+// oracle have it -- and adds +0 to it: a product that is exactly -0 (an earlier partial product underflowed to -0) came out as +0.
+// (op_assign.hip fences its axpy for the same instruction.)
+template <typename T>
+__device__ __forceinline__ T narrow_result(float r) {
+    if constexpr (sizeof(T) != 4) asm volatile("" : "+v"(r));
+    return (T)r;
+}
+
 // 32 physical lanes x 4 elements per vector, at any element-aligned base.
 template <int OP, typename T, bool AL>
 __global__ __launch_bounds__(kThreads) void reduce_rows4(const T *__restrict__ base, uint32_t n, uint32_t ncols,
@@ -101,7 +111,7 @@ __global__ __launch_bounds__(kThreads) void reduce_rows4(const T *__restrict__ b
     acc[0] = r_red<OP>(acc[0], acc[2]);
     acc[1] = r_red<OP>(acc[1], acc[3]);
     acc[0] = r_red<OP>(acc[0], acc[1]);
-    if (p == 0) results[q] = (T)acc[0];
+    if (p == 0) results[q] = narrow_result<T>(acc[0]);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -187,7 +197,7 @@ __global__ __launch_bounds__(kLongThreads) void reduce_long(const T *__restrict_
     acc = r_red<OP>(acc, upper[lane]);
 #pragma unroll
     for (int sft = 32; sft >= 1; sft >>= 1) acc = r_red<OP>(acc, __shfl_down(acc, sft, 64));
-    if (lane == 0) results[q] = (T)acc;
+    if (lane == 0) results[q] = narrow_result<T>(acc);
 }
 
 template <int OP, typename T>
@@ -271,7 +281,7 @@ __global__ __launch_bounds__(kThreads) void reduce_fast_pass2(const float *__res
     float acc = r_init<OP>();
     for (uint32_t i = threadIdx.x; i < nparts; i += kThreads) acc = r_red<OP>(acc, partial[i]);
     const float r = fast_block_fold<OP>(acc);
-    if (threadIdx.x == 0) result[0] = (T)r;
+    if (threadIdx.x == 0) result[0] = narrow_result<T>(r);
 }
 
 template <int OP, typename T>

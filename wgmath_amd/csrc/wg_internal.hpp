@@ -244,6 +244,9 @@ int wgk_gemm_f32_nt(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nm
 // on m1 / m2, then wgk_gemm_f16 with `panels`). WG_ERR_UNSUPPORTED without a message: not that kind of product, launch panel by panel.
 int wg_gemm_f16_panels(wg_ctx *ctx, bool tr, void *out_panel0, uint32_t ldc, const wg_buf *m1, wg_view_shape m1_shape, const wg_buf *m2, wg_view_shape m2_shape,
                        const wgk_panels &panels);
+// The aliasing rule (api.hip's check_alias) for callers outside the operator front-end: WG_ERR_ALIASED with "op: `wname` overlaps `rname`" when the written view shares a
+// byte with the read one; base_*: element 0 of each view's buffer.
+int wg_check_alias(const char *op, wg_dtype dtype, const char *wname, wg_view_shape w, const void *base_w, const char *rname, wg_view_shape r, const void *base_r);
 
 // split-K (the plan: gemm16_plan.hip; the reduce kernels: splitk.hip)
 uint32_t wg_splitk_plan(uint64_t tiles, uint32_t slots, uint32_t k_units, uint32_t min_units, uint64_t out_elems, uint64_t max_ws_bytes);
