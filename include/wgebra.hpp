@@ -433,6 +433,22 @@ struct Gemv {
     void dispatch_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<T> out, GpuTensorView<T> m, GpuTensorView<T> v) const {
         dispatch_generic(d, s, p, out, m, v, GemvVariant::GemvTr);
     }
+    // extension (wg_gemv_mixed): a matrix of 16-bit weights W (_Float16 / bf16; float forwards to wg_gemv) with f32 vectors and an f32 result -- the matrix is
+    // widened exactly, v is never narrowed, the f32 accumulator is stored as it is. Column-major views (the row-major surface has no mixed form).
+    template <typename W>
+    void dispatch_mixed_generic(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<float> out, GpuTensorView<W> m,
+                                GpuTensorView<float> v, GemvVariant variant) const {
+        check(wg_gemv_mixed(pass.ctx(), (wg_gemv_variant)variant, dtype_of<W>::value, out.buffer(), out.shape(), m.buffer(), m.shape(), v.buffer(),
+                            v.shape()));
+    }
+    template <typename W>
+    void dispatch_mixed(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<W> m, GpuTensorView<float> v) const {
+        dispatch_mixed_generic(d, s, p, out, m, v, GemvVariant::Gemv);
+    }
+    template <typename W>
+    void dispatch_mixed_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<W> m, GpuTensorView<float> v) const {
+        dispatch_mixed_generic(d, s, p, out, m, v, GemvVariant::GemvTr);
+    }
 };
 
 // reduce.rs:62-113

@@ -53,7 +53,7 @@ extern "C" {
 #define WGEBRA_HIP_ABI_VERSION 5 /* 5: wg_debug_take_path; and the round-6 additions that came without a bump: wg_copy_view, wg_timestamps_reserve,
                                     wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE, wg_debug_gemm16_plan (an added diagnostic symbol with its two structs); WG_ERR_ALIASED = 9 (an appended status: calls that
                                     return it used to launch kernels that raced on their own operands) with wg_debug_views_overlap; and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
-                                    that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump);
+                                    that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump); wg_gemv_mixed (an added symbol);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
 
@@ -208,7 +208,7 @@ int wg_debug_mfma_ceiling(wg_ctx *ctx, double min_seconds, double *tflops, doubl
  * "f32.big/ns=4 splitk.reduce/ns=4", "f16.cont", "f16.pad/c=seed>f16.t128/ns=1" (a tag ending in '>' wraps the next one: staging, padding, transposed
  * forms). Gemv names its kernel instance: "gemv> f32.gemv gemv.n/t=4,ns=3 gemv.combine/ns=3", "gemv.small/rl=8", "gemv.t/t=8,ns=1",
  * "gemv.tcols/e=8,u=4,v=2,ns=1" (elements per load, loads in flight, right-hand sides), "gemv.tlds/nr=4,c=2,th=1024", "gemv.small_reduce/rl=4",
- * "gemv_reduce.two>" (wg_gemv_reduce as Gemv, then Reduce), "gemv_any/t,ns=2" (views the vec4 kernels cannot take); Reduce: "reduce.long",
+ * "gemv> f16w.gemv gemv.tcols/e=8,u=8,v=1,ns=1" (wg_gemv_mixed: 16-bit weights, f32 vectors), "gemv_reduce.two>" (wg_gemv_reduce as Gemv, then Reduce), "gemv_any/t,ns=2" (views the vec4 kernels cannot take); Reduce: "reduce.long",
  * "reduce.rows4/al=1" (al: the aligned vec4 instance), "reduce.fast/np=64". Equal logs mean the same kernels in the same summation order. Host-side bookkeeping only; the context keeps the newest few hundred bytes.
  * Copies the log into buf (NUL-terminated, truncated to cap - 1 bytes) and clears it; buf may be NULL to just clear it. */
 int wg_debug_take_path(wg_ctx *ctx, char *buf, size_t cap);
@@ -395,6 +395,34 @@ int wg_gemv(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype,
             wg_buf *out, wg_view_shape out_shape,
             const wg_buf *m, wg_view_shape m_shape,
             const wg_buf *v, wg_view_shape v_shape);
+
+/*
+ * Extension: mixed-precision Gemv -- a 16-bit matrix, f32 vectors and an f32 result (the decode step of an inference stack: weights stored in f16 / bf16,
+ * activations kept in f32). `m` holds m_dtype elements (WG_F16 or WG_BF16); `v` and `out` hold f32; every view shape counts elements of its own operand's type,
+ * and the bounds checks use each operand's own element size. m_dtype == WG_F32 forwards to wg_gemv(.., WG_F32, ..) unchanged (a caller generic over the weight
+ * type needs no branch). Everything else is wg_gemv's contract, with its status codes and messages: the two dimension checks, *_FAST with out rows % 4 != 0
+ * (PRECONDITION), WG_GEMV_TR_FAST falling back to WG_GEMV_TR, zero-sized buffers / views skipped with WG_OK, right-hand sides and batch taken from `out`.
+ * Arithmetic:
+ *   - matrix elements are widened exactly; `v` is read as the f32 it is and never narrowed; products and sums are f32 FMAs; the result is stored as the f32
+ *     accumulator -- there is no rounding step;
+ *   - `out` is overwritten (NaN / Inf already in it do not survive); an Inf or NaN in the last valid column or row of `m` reaches only the results the
+ *     mathematics says it reaches (load slots past the end contribute an exact zero);
+ *   - deterministic: no atomics, a fixed summation order -- two calls give identical bits;
+ *   - the kernels and the summation order are those the 16-bit wg_gemv picks for the same shape, views and context (the plan is made with the MATRIX's
+ *     element size): while that call stays on the Gemv kernels the accumulators are the same bit for bit, and one round-to-nearest-even of this call's result
+ *     reproduces its result whenever `v` is representable in the 16-bit type.
+ * Right-hand sides: this call NEVER takes the Gemm kernels (they would round `v` to 16 bits). Up to 8 right-hand sides share one pass over the matrix; more
+ * run as groups of 8 on the Gemv kernels, one pass over the matrix per group. nmats * ceil(nrhs / 8) > 65535 is WG_ERR_UNSUPPORTED.
+ * Views that are not vec4-aligned, per operand as in wg_gemv: a matrix that is off (offset, leading dimension, lengths) runs where it lies (gemv_any.hip's
+ * mixed instances); vectors or an `out` that are off are staged as f32 copies in a context scratch that cannot grow inside a recording (WG_ERR_WORKSPACE).
+ *   ALIASED       : `out` shares a byte with the part of `m` or of `v` the call addresses -- on addresses, so `out` and `m` may live in one buffer although
+ *                   their element sizes differ (compared in 2-byte units, with the bound of the aliasing rule).
+ * wg_debug_take_path: the element prefix is "f16w.gemv" / "bf16w.gemv" (w: 16-bit weights only), followed by the dtype-free tags of wg_gemv.
+ */
+int wg_gemv_mixed(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype m_dtype,
+                  wg_buf *out, wg_view_shape out_shape,
+                  const wg_buf *m, wg_view_shape m_shape,
+                  const wg_buf *v, wg_view_shape v_shape);
 
 /*
  * ROW_MAJOR operator surface. Replaces composing the reference's shaders with

@@ -34,12 +34,22 @@ inline wg_view_shape shape_of(const View &v) {
     s.size[0] = v.rows; s.size[1] = v.cols; s.size[2] = v.mats; s.stride = v.stride; s.stride_mat = v.stride_mat; s.offset = v.offset;
     return s;
 }
-int check_alias(const char *op, wg_dtype dt, const char *wname, const View &w, const void *base_w, const char *rname, const View &r, const void *base_r) {
-    int exact = 1;
-    if (!wg_views_overlap(shape_of(w), (uint64_t)(uintptr_t)base_w, shape_of(r), (uint64_t)(uintptr_t)base_r, (uint32_t)wg_dtype_size(dt), &exact)) return WG_OK;
+// (the one place that words WG_ERR_ALIASED: every operator and both element-size forms below report through it)
+int aliased(const char *op, const char *wname, const char *rname, int exact) {
     if (exact) return wg_set_error(WG_ERR_ALIASED, "%s: `%s` overlaps `%s` (the written view shares memory with a view the call reads)", op, wname, rname);
     return wg_set_error(WG_ERR_ALIASED, "%s: `%s` may overlap `%s` (their byte ranges intersect and they have more than %d column runs between them: not decided exactly)", op,
                         wname, rname, WG_VIEWS_OVERLAP_MAX_RUNS);
+}
+int check_alias(const char *op, wg_dtype dt, const char *wname, const View &w, const void *base_w, const char *rname, const View &r, const void *base_r) {
+    int exact = 1;
+    if (!wg_views_overlap(shape_of(w), (uint64_t)(uintptr_t)base_w, shape_of(r), (uint64_t)(uintptr_t)base_r, (uint32_t)wg_dtype_size(dt), &exact)) return WG_OK;
+    return aliased(op, wname, rname, exact);
+}
+// ... for a written f32 view against a read view of 16-bit elements (wg_gemv_mixed: `out` and `m` may live in one buffer): in 2-byte units (views_overlap.hpp)
+int check_alias_f32_u16(const char *op, const char *wname, const View &w, const void *base_w, const char *rname, const View &r, const void *base_r) {
+    int exact = 1;
+    if (!wg_views_overlap_f32_u16(shape_of(w), (uint64_t)(uintptr_t)base_w, shape_of(r), (uint64_t)(uintptr_t)base_r, &exact)) return WG_OK;
+    return aliased(op, wname, rname, exact);
 }
 inline View one_element() { return View{ 1, 1, 1, 1, 1, 0 }; } // the result scalar of a Reduce: element 0 of its buffer
 
@@ -155,6 +165,38 @@ int gemv_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, wg_buf *out, const View &o
     if (int rc = wgk_gemv(ctx, tr, dtype, Op, Kp, nrhs, mats, O, ldo, o_batch, Mx, Vx)) return rc;
     if (!so) return WG_OK;
     return wgk_stage_copy(ctx, dtype, (void *)elem_ptr(out, o.offset, dtype), o.stride, o.stride_mat, rows_out, nrhs, op, Op, oe, Op, nrhs, mats);
+}
+
+// wg_gemv_mixed on views the vec4 kernels cannot address: gemv_staged with an element type per operand (the matrix md, vectors and result f32)
+int gemv_mixed_staged(wg_ctx *ctx, bool tr, wg_dtype md, wg_buf *out, const View &o, const wg_buf *m, const View &mm, const wg_buf *v, const View &vv, uint32_t rows_out,
+                      uint32_t k) {
+    const uint32_t Op = rows_out % 4 ? up8(rows_out) : rows_out, Kp = k % 4 ? up8(k) : k, nrhs = o.cols, mats = o.mats;
+    const bool sm = !vec4_ok(mm) || Op != rows_out || Kp != k, sv = !vec4_ok(vv), so = !vec4_ok(o);
+    const uint64_t ve = sv ? (uint64_t)Kp * nrhs : 0, oe = so ? (uint64_t)Op * nrhs : 0;
+    if (ve * mats >= (1ull << 32) || oe * mats >= (1ull << 32))
+        return wg_set_error(WG_ERR_UNSUPPORTED, "Gemv: operands too large for the staging path of views that are not vec4-aligned");
+    float *O = (float *)elem_ptr(out, o.offset, WG_F32);
+    wgk_mat Mx = { elem_ptr(m, mm.offset, md), mm.stride, mm.stride_mat }, Vx = { elem_ptr(v, vv.offset, WG_F32), vv.stride, vv.stride_mat };
+    if (sm) { // the matrix where it lies, vectors and result element by element (gemv_any.hip)
+        if (k == 0) return wgk_stage_copy(ctx, WG_F32, O, o.stride, o.stride_mat, rows_out, nrhs, out->ptr, 1, 0, 0, 0, mats); // (an empty sum)
+        return wgk_gemv_any_mixed(ctx, tr, md, mm.rows, mm.cols, nrhs, mats, O, o.stride, o.stride_mat, Mx, Vx);
+    }
+    // (lengths are multiples of 4 here: Op == rows_out, Kp == k) f32 copies of the vectors / the result that are off
+    void *ws = nullptr;
+    if (int rc = wg_ctx_stage_workspace(ctx, (size_t)((ve + oe) * mats * sizeof(float)), &ws)) return rc;
+    float *vp = (float *)ws, *op = vp + ve * mats;
+    uint32_t ldo = o.stride;
+    uint64_t o_batch = o.stride_mat;
+    float *Ox = O;
+    if (sv) {
+        if (int rc = wgk_stage_copy(ctx, WG_F32, vp, Kp, ve, Kp, nrhs, Vx.ptr, vv.stride, vv.stride_mat, k, nrhs, mats)) return rc;
+        Vx = wgk_mat{ vp, Kp, ve };
+    }
+    if (so) { Ox = op; ldo = Op; o_batch = oe; }
+    wg_path(ctx, "stage>");
+    if (int rc = wgk_gemv_mixed(ctx, tr, md, Op, Kp, nrhs, mats, Ox, ldo, o_batch, Mx, Vx)) return rc;
+    if (!so) return WG_OK;
+    return wgk_stage_copy(ctx, WG_F32, O, o.stride, o.stride_mat, rows_out, nrhs, op, Op, oe, Op, nrhs, mats);
 }
 
 } // namespace
@@ -280,6 +322,44 @@ int wg_gemv(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype, wg_buf *out, w
     wgk_mat M = { elem_ptr(m, mm.offset, dtype), mm.stride, mm.stride_mat };
     wgk_mat V = { elem_ptr(v, vv.offset, dtype), vv.stride, vv.stride_mat };
     return wgk_gemv(ctx, tr, dtype, o.rows, m_cols, o.cols, o.mats, (void *)elem_ptr(out, o.offset, dtype), o.stride, o.stride_mat, M, V);
+}
+
+// wg_gemv with an element type per operand: `m` holds m_dtype elements (f16 / bf16), `v` and `out` f32. The same checks in the same order with the same messages;
+// bounds per operand's own element size; the aliasing rule on addresses (out against the 16-bit matrix in 2-byte units).
+int wg_gemv_mixed(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype m_dtype, wg_buf *out, wg_view_shape out_shape, const wg_buf *m, wg_view_shape m_shape,
+                  const wg_buf *v, wg_view_shape v_shape) {
+    const wg_buf *bufs[3] = { out, m, v };
+    if (int rc = check_common("Gemv", ctx, m_dtype, bufs, 3)) return rc;
+    if (m_dtype == WG_F32) return wg_gemv(ctx, variant, WG_F32, out, out_shape, m, m_shape, v, v_shape); // (a caller generic over the weight type needs no branch)
+    if ((int)variant < 0 || (int)variant > 3) return wg_set_error(WG_ERR_INVALID_ARG, "Gemv: unknown variant %d", (int)variant);
+    const bool tr = variant == WG_GEMV_TR || variant == WG_GEMV_TR_FAST;
+    const View o = mk(out_shape), mm = mk(m_shape), vv = mk(v_shape);
+
+    const uint32_t m_rows = tr ? mm.cols : mm.rows, m_cols = tr ? mm.rows : mm.cols;
+    if (m_cols != vv.rows || m_rows != o.rows)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemv: dimension mismatch. (out [%u,%u,%u], m [%u,%u,%u]%s, v [%u,%u,%u])", o.rows,
+                            o.cols, o.mats, mm.rows, mm.cols, mm.mats, tr ? "^T" : "", vv.rows, vv.cols, vv.mats);
+    if (variant == WG_GEMV_TR_FAST && mm.rows % 128u != 0) variant = WG_GEMV_TR;
+    if ((variant == WG_GEMV_FAST || variant == WG_GEMV_TR_FAST) && o.rows % 4u != 0)
+        return wg_set_error(WG_ERR_PRECONDITION, "Gemv: assertion `left == right` failed (out_nrows %% 4 == 0, gemv.rs:122): out has %u rows",
+                            o.rows);
+    if (out->bytes == 0 || m->bytes == 0 || v->bytes == 0) return WG_OK;
+    if (o.rows == 0 || o.cols == 0 || o.mats == 0) return WG_OK;
+
+    const View m_eff = { mm.rows, mm.cols, o.mats, mm.stride, mm.stride_mat, mm.offset };
+    const View v_eff = { vv.rows, o.cols, o.mats, vv.stride, vv.stride_mat, vv.offset };
+    if (int rc = check_bounds("Gemv", "out", o, out, WG_F32)) return rc;
+    if (int rc = check_bounds("Gemv", "m", m_eff, m, m_dtype)) return rc;
+    if (int rc = check_bounds("Gemv", "v", v_eff, v, WG_F32)) return rc;
+    if (int rc = check_alias_f32_u16("Gemv", "out", o, out->ptr, "m", m_eff, m->ptr)) return rc;
+    if (int rc = check_alias("Gemv", WG_F32, "out", o, out->ptr, "v", v_eff, v->ptr)) return rc;
+
+    WG_HIP_TRY(hipSetDevice(ctx->device));
+    if (!vec4_ok(o) || !vec4_ok(m_eff) || !vec4_ok(v_eff) || m_cols % 4 || m_rows % 4)
+        return gemv_mixed_staged(ctx, tr, m_dtype, out, o, m, m_eff, v, v_eff, m_rows, m_cols);
+    wgk_mat M = { elem_ptr(m, mm.offset, m_dtype), mm.stride, mm.stride_mat };
+    wgk_mat V = { elem_ptr(v, vv.offset, WG_F32), vv.stride, vv.stride_mat };
+    return wgk_gemv_mixed(ctx, tr, m_dtype, o.rows, m_cols, o.cols, o.mats, (float *)elem_ptr(out, o.offset, WG_F32), o.stride, o.stride_mat, M, V);
 }
 
 int wg_reduce(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype, const wg_buf *value, wg_view_shape value_shape, wg_buf *result) {

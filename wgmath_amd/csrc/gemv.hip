@@ -22,6 +22,7 @@
 #include "wg_internal.hpp"
 #include "reduce_ops.hpp"
 #include <cstdlib>
+#include <type_traits>
 
 namespace {
 
@@ -82,11 +83,13 @@ __device__ __forceinline__ float wave_sum(float x) {
     return x;
 }
 
-template <typename T>
+// T: the matrix's element type; V: the vectors' and the result's (T, or float beside a 16-bit matrix -- wg_gemv_mixed: every kernel widens what it loads to float,
+// accumulates in float and narrows only in store4, so the mixed instances differ in the loads of v and in the store, nowhere else)
+template <typename T, typename V = T>
 struct GemvArgsT {
     const T *m; uint32_t ldm; uint64_t m_batch;
-    const T *v; uint32_t ldv; uint64_t v_batch;
-    T *out;          // the result (written when part == nullptr) ...
+    const V *v; uint32_t ldv; uint64_t v_batch;
+    V *out;          // the result (written when part == nullptr) ...
     float *part;     // ... or the f32 partials buffer when nsplit > 1
     uint32_t ld_dst; // elements between RHS columns of the destination
     uint64_t dst_batch;
@@ -102,8 +105,15 @@ using GemvArgs = GemvArgsT<float>;
 // N: dst[r] = sum_c m[r, c] v[c],  r in this block's 256 rows, c in this split's column range
 // grid = (row blocks, splits, nmats * rhs groups)
 // ------------------------------------------------------------------------------------------------------
-template <int NRHS, typename T>
-__global__ __launch_bounds__(kThreads) void gemv_n_kernel(GemvArgsT<T> a) {
+// (This kernel names its element types through ONE template argument -- E: an element type, or MixedElems<matrix type, vector type> --, so that the instances of one
+// element type keep their two-argument names: the ISA checks of the test suite find gemv_n_kernel<1, float> by its mangled name.)
+template <typename T, typename V> struct MixedElems {};
+template <typename E> struct gemv_elems { typedef E M; typedef E V; };
+template <typename Tm, typename Tv> struct gemv_elems<MixedElems<Tm, Tv>> { typedef Tm M; typedef Tv V; };
+template <int NRHS, typename E>
+__global__ __launch_bounds__(kThreads) void gemv_n_kernel(GemvArgsT<typename gemv_elems<E>::M, typename gemv_elems<E>::V> a) {
+    typedef typename gemv_elems<E>::M T;
+    typedef typename gemv_elems<E>::V V;
     __shared__ float4 part[kWaves][NRHS][64];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -121,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void gemv_n_kernel(GemvArgsT<T> a) {
     const uint32_t w_end = min(c_end, w_begin + per_wave);
 
     const T *mp = a.m + z * a.m_batch + (row_ok ? row : 0u);
-    const T *vp = a.v + z * a.v_batch;
+    const V *vp = a.v + z * a.v_batch;
 
     float4 acc[NRHS];
 #pragma unroll
@@ -191,8 +201,8 @@ __global__ __launch_bounds__(kThreads) void gemv_n_kernel(GemvArgsT<T> a) {
 // T: dst[c] = sum_r m[r, c] v[r],  4 columns per wave, rows of this split
 // grid = (column groups of 16, splits, nmats * rhs groups)
 // ------------------------------------------------------------------------------------------------------
-template <int NRHS, typename T>
-__global__ __launch_bounds__(kThreads) void gemv_t_kernel(GemvArgsT<T> a) {
+template <int NRHS, typename T, typename V = T>
+__global__ __launch_bounds__(kThreads) void gemv_t_kernel(GemvArgsT<T, V> a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t rhs_groups = (a.nrhs + kMaxRhs - 1) / kMaxRhs;
@@ -204,7 +214,7 @@ __global__ __launch_bounds__(kThreads) void gemv_t_kernel(GemvArgsT<T> a) {
     const uint32_t r_end = min(a.k, r_begin + a.k_per_split);
 
     const T *mp = a.m + z * a.m_batch + (uint64_t)col0 * a.ldm;
-    const T *vp = a.v + z * a.v_batch;
+    const V *vp = a.v + z * a.v_batch;
     const uint64_t ld4 = a.ldm; // elements between columns
 
     float acc[4][NRHS];
@@ -294,8 +304,16 @@ __device__ __forceinline__ RowPiece<E, T> piece_cached(const T *p) {
     }
     return o;
 }
-template <typename T, int E, int U = WG_GEMVT_U, int NRHS = 1>
-__global__ __launch_bounds__(kThreads) void gemv_t_cols_kernel(GemvArgsT<T> a) {
+// (f32 vectors beside a 16-bit matrix, E = 8: a lane's 8 matrix rows meet 8 f32 vector entries -- two 16-byte loads)
+template <>
+__device__ __forceinline__ RowPiece<8, float> piece_cached<8, float>(const float *p) {
+    RowPiece<8, float> o;
+    const float4 lo = load4(p), hi = load4(p + 4);
+    o.f[0] = lo.x; o.f[1] = lo.y; o.f[2] = lo.z; o.f[3] = lo.w; o.f[4] = hi.x; o.f[5] = hi.y; o.f[6] = hi.z; o.f[7] = hi.w;
+    return o;
+}
+template <typename T, int E, int U = WG_GEMVT_U, int NRHS = 1, typename V = T>
+__global__ __launch_bounds__(kThreads) void gemv_t_cols_kernel(GemvArgsT<T, V> a) {
     const uint32_t col = blockIdx.x * (kThreads / 32) + (threadIdx.x >> 5);
     const uint32_t p = threadIdx.x & 31u;
     const uint32_t z = blockIdx.z;
@@ -303,7 +321,7 @@ __global__ __launch_bounds__(kThreads) void gemv_t_cols_kernel(GemvArgsT<T> a) {
     const uint32_t r_begin = blockIdx.y * a.k_per_split;
     const uint32_t r_end = min(a.k, r_begin + a.k_per_split);
     const T *mp = a.m + z * a.m_batch + (uint64_t)col * a.ldm;
-    const T *vp = a.v + z * a.v_batch;
+    const V *vp = a.v + z * a.v_batch;
     // U loads in flight per lane per trip. Columns of at most 4 chunks take the U = 4 instantiation (the launcher): half the registers, twice the half-waves per CU -- what
     // a short column lacks in loads per half-wave it gets back in half-waves (f16 GemvTr 1024 x 65536: 55 us in the tail loop, 40 us as a partial trip of U = 8, see the bench line)
     constexpr uint32_t kChunk = 32u * E;   // rows a half-wave covers per load
@@ -321,13 +339,14 @@ __global__ __launch_bounds__(kThreads) void gemv_t_cols_kernel(GemvArgsT<T> a) {
         uint32_t j = i + rot;
         if (j >= nblocks) j -= nblocks;
         const uint32_t r = r_begin + j * kBlock + E * p;
-        RowPiece<E, T> mv[U], xv[NRHS][U];
+        RowPiece<E, T> mv[U];
+        RowPiece<E, V> xv[NRHS][U];
 #pragma unroll
         for (int u = 0; u < U; ++u) mv[u] = piece_stream<E, T>(mp + r + kChunk * u);
 #pragma unroll
         for (int y = 0; y < NRHS; ++y)
 #pragma unroll
-            for (int u = 0; u < U; ++u) xv[y][u] = piece_cached<E, T>(vp + (uint64_t)y * a.ldv + r + kChunk * u);
+            for (int u = 0; u < U; ++u) xv[y][u] = piece_cached<E, V>(vp + (uint64_t)y * a.ldv + r + kChunk * u);
 #pragma unroll
         for (int u = 0; u < U; ++u)
 #pragma unroll
@@ -340,7 +359,8 @@ __global__ __launch_bounds__(kThreads) void gemv_t_cols_kernel(GemvArgsT<T> a) {
     const uint32_t rem_chunks = ((r_end - r_begin) - nblocks * kBlock) / kChunk; // < U, wave-uniform
     if (rem_chunks) {
         const uint32_t r = r_begin + nblocks * kBlock + E * p;
-        RowPiece<E, T> mv[U], xv[NRHS][U];
+        RowPiece<E, T> mv[U];
+        RowPiece<E, V> xv[NRHS][U];
 #pragma unroll
         for (int u = 0; u < U - 1; ++u)
             if ((uint32_t)u < rem_chunks) mv[u] = piece_stream<E, T>(mp + r + kChunk * u);
@@ -348,7 +368,7 @@ __global__ __launch_bounds__(kThreads) void gemv_t_cols_kernel(GemvArgsT<T> a) {
         for (int y = 0; y < NRHS; ++y)
 #pragma unroll
             for (int u = 0; u < U - 1; ++u)
-                if ((uint32_t)u < rem_chunks) xv[y][u] = piece_cached<E, T>(vp + (uint64_t)y * a.ldv + r + kChunk * u);
+                if ((uint32_t)u < rem_chunks) xv[y][u] = piece_cached<E, V>(vp + (uint64_t)y * a.ldv + r + kChunk * u);
 #pragma unroll
         for (int u = 0; u < U - 1; ++u)
             if ((uint32_t)u < rem_chunks) {
@@ -379,7 +399,7 @@ __global__ __launch_bounds__(kThreads) void gemv_t_cols_kernel(GemvArgsT<T> a) {
         for (int sh = 16; sh >= 1; sh >>= 1) s += __shfl_xor(s, sh, 64);
         if (p == 0) {
             const uint64_t off = z * a.dst_batch + blockIdx.y * a.dst_split + (uint64_t)y * a.ld_dst + col;
-            if (a.part) a.part[off] = s; else a.out[off] = (T)s;
+            if (a.part) a.part[off] = s; else a.out[off] = (V)s;
         }
     }
 }
@@ -552,8 +572,8 @@ __global__ __launch_bounds__(kThreads) void gemv_combine_kernel(const float *__r
 // instead of eight -- the kernel was latency-bound at 32 workgroups of 32 rows).
 // gemv_small_rows is shared with the fused Gemv + Reduce below: same summation, same bits.
 // ------------------------------------------------------------------------------------------------------
-template <int RL, typename T>
-__device__ __forceinline__ float4 gemv_small_rows(const T *mp, uint32_t ldm, const T *vp, uint32_t k, float4 (*red)[8]) {
+template <int RL, typename T, typename V = T>
+__device__ __forceinline__ float4 gemv_small_rows(const T *mp, uint32_t ldm, const V *vp, uint32_t k, float4 (*red)[8]) {
     constexpr uint32_t G = 256u / RL; // column groups of the workgroup
     const uint32_t rl = threadIdx.x & (RL - 1u), g = threadIdx.x / RL;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -588,16 +608,16 @@ static inline int gemv_small_rl(uint32_t rows_out) {
     return rows_out >= 4096u ? 8 : (rows_out >= 2048u ? 4 : 2);
 }
 
-template <int RL, typename T>
-__global__ __launch_bounds__(kThreads) void gemv_n_small_kernel(GemvArgsT<T> a) {
+template <int RL, typename T, typename V = T>
+__global__ __launch_bounds__(kThreads) void gemv_n_small_kernel(GemvArgsT<T, V> a) {
     __shared__ float4 red[4][8];
     const uint32_t rl = threadIdx.x & (RL - 1u);
     const uint32_t z = blockIdx.z, y = blockIdx.y;
     const uint32_t row = blockIdx.x * (4u * RL) + 4u * rl;
     const bool row_ok = row < a.rows_out;
     const T *mp = a.m + z * a.m_batch + (row_ok ? row : 0u);
-    const T *vp = a.v + z * a.v_batch + (uint64_t)y * a.ldv;
-    const float4 s = gemv_small_rows<RL, T>(mp, a.ldm, vp, a.k, red);
+    const V *vp = a.v + z * a.v_batch + (uint64_t)y * a.ldv;
+    const float4 s = gemv_small_rows<RL, T, V>(mp, a.ldm, vp, a.k, red);
     if (threadIdx.x < (uint32_t)RL && row_ok) store4(a.out + z * a.dst_batch + (uint64_t)y * a.ld_dst + row, s);
 }
 
@@ -727,8 +747,9 @@ static bool uses_small_kernel(int cus, bool trans, uint32_t rows_out, uint32_t k
 
 } // namespace
 
-template <typename T>
-static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, T *out, uint32_t out_ld, uint64_t out_batch,
+// (V != T: the mixed call -- the plan below is made with the MATRIX's element type, so it is the plan of gemv_launch<T> for the same shape, views and context)
+template <typename T, typename V = T>
+static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, V *out, uint32_t out_ld, uint64_t out_batch,
                        wgk_mat m, wgk_mat v) {
     const int cus = ctx->compute_units > 0 ? ctx->compute_units : 256;
     const uint32_t rhs_groups = ceil_div(nrhs, kMaxRhs);
@@ -742,9 +763,9 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
     uint32_t k_per_split = k == 0 ? 4u : ceil_div(ceil_div(k, nsplit), 4u) * 4u; // vec4 granularity
     nsplit = k == 0 ? 1u : ceil_div(k, k_per_split);
 
-    GemvArgsT<T> a;
+    GemvArgsT<T, V> a;
     a.m = (const T *)m.ptr; a.ldm = m.ld; a.m_batch = m.batch;
-    a.v = (const T *)v.ptr; a.ldv = v.ld; a.v_batch = v.batch;
+    a.v = (const V *)v.ptr; a.ldv = v.ld; a.v_batch = v.batch;
     a.rows_out = rows_out; a.k = k; a.nrhs = nrhs; a.k_per_split = k_per_split;
     a.out = out;
     a.part = nullptr;
@@ -769,9 +790,9 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
         const int rl = gemv_small_rl(rows_out);
         wg_path(ctx, "gemv.small/rl=%d", rl);
         const dim3 sg(ceil_div(rows_out, 4u * (uint32_t)rl), nrhs, nmats);
-        if (rl == 8) hipLaunchKernelGGL((gemv_n_small_kernel<8, T>), sg, dim3(kThreads), 0, ctx->stream, a);
-        else if (rl == 4) hipLaunchKernelGGL((gemv_n_small_kernel<4, T>), sg, dim3(kThreads), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((gemv_n_small_kernel<2, T>), sg, dim3(kThreads), 0, ctx->stream, a);
+        if (rl == 8) hipLaunchKernelGGL((gemv_n_small_kernel<8, T, V>), sg, dim3(kThreads), 0, ctx->stream, a);
+        else if (rl == 4) hipLaunchKernelGGL((gemv_n_small_kernel<4, T, V>), sg, dim3(kThreads), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((gemv_n_small_kernel<2, T, V>), sg, dim3(kThreads), 0, ctx->stream, a);
         WG_HIP_TRY(hipGetLastError());
         return WG_OK;
     }
@@ -782,43 +803,48 @@ static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, u
     const int tile = per_group > 4 ? 8 : (per_group > 2 ? 4 : (int)per_group);
     if (t_cols) {
         // f16: 16-byte loads (8 rows per lane) where every column, split and batch keeps them aligned; 8-byte loads (the view contract) otherwise
+        // (v16: elements of the vectors' type per 16 bytes -- f32 vectors beside a 16-bit matrix are read as two 16-byte loads per 8 rows)
         bool wide = false;
+        constexpr uint32_t v16 = 16u / sizeof(V);
         if constexpr (sizeof(T) == 2)
-            wide = (uintptr_t)a.m % 16 == 0 && (uintptr_t)a.v % 16 == 0 && a.ldm % 8 == 0 && a.k_per_split % 8 == 0 && (nmats == 1 || (a.m_batch % 8 == 0 && a.v_batch % 8 == 0)) &&
-                   (nrhs == 1 || a.ldv % 8 == 0);
+            wide = (uintptr_t)a.m % 16 == 0 && (uintptr_t)a.v % 16 == 0 && a.ldm % 8 == 0 && a.k_per_split % 8 == 0 && (nmats == 1 || (a.m_batch % 8 == 0 && a.v_batch % v16 == 0)) &&
+                   (nrhs == 1 || a.ldv % v16 == 0);
         // (the tag names the instance the branches below launch: elements per load, loads in flight, right-hand sides)
         const int te = wide ? 8 : 4, tu = nrhs == 2 || t_cols_u4(a.k_per_split, (uint32_t)te) ? 4 : WG_GEMVT_U;
         wg_path(ctx, "gemv.tcols/e=%d,u=%d,v=%u,ns=%u", te, tu, nrhs, nsplit);
         if (nrhs == 2) { // (uses_t_cols2)
             if constexpr (sizeof(T) == 2) {
-                if (wide) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, 4, 2>), grid, block, 0, ctx->stream, a);
-                else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 2>), grid, block, 0, ctx->stream, a);
-            } else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 2>), grid, block, 0, ctx->stream, a);
+                if (wide) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, 4, 2, V>), grid, block, 0, ctx->stream, a);
+                else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 2, V>), grid, block, 0, ctx->stream, a);
+            } else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 2, V>), grid, block, 0, ctx->stream, a);
         } else if constexpr (sizeof(T) == 2) {
-            if (wide && t_cols_u4(a.k_per_split, 8u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, 4>), grid, block, 0, ctx->stream, a);
-            else if (wide) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8>), grid, block, 0, ctx->stream, a);
-            else if (t_cols_u4(a.k_per_split, 4u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4>), grid, block, 0, ctx->stream, a);
-        } else if (t_cols_u4(a.k_per_split, 4u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4>), grid, block, 0, ctx->stream, a);
+            if (wide && t_cols_u4(a.k_per_split, 8u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, 4, 1, V>), grid, block, 0, ctx->stream, a);
+            else if (wide) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, WG_GEMVT_U, 1, V>), grid, block, 0, ctx->stream, a);
+            else if (t_cols_u4(a.k_per_split, 4u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 1, V>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, WG_GEMVT_U, 1, V>), grid, block, 0, ctx->stream, a);
+        } else if (t_cols_u4(a.k_per_split, 4u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 1, V>), grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, WG_GEMVT_U, 1, V>), grid, block, 0, ctx->stream, a);
     }
     else if (trans) {
         wg_path(ctx, "gemv.t/t=%d,ns=%u", tile, nsplit);
-        if (tile == 1) hipLaunchKernelGGL((gemv_t_kernel<1, T>), grid, block, 0, ctx->stream, a);
-        else if (tile == 2) hipLaunchKernelGGL((gemv_t_kernel<2, T>), grid, block, 0, ctx->stream, a);
-        else if (tile == 4) hipLaunchKernelGGL((gemv_t_kernel<4, T>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((gemv_t_kernel<8, T>), grid, block, 0, ctx->stream, a);
+        if (tile == 1) hipLaunchKernelGGL((gemv_t_kernel<1, T, V>), grid, block, 0, ctx->stream, a);
+        else if (tile == 2) hipLaunchKernelGGL((gemv_t_kernel<2, T, V>), grid, block, 0, ctx->stream, a);
+        else if (tile == 4) hipLaunchKernelGGL((gemv_t_kernel<4, T, V>), grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((gemv_t_kernel<8, T, V>), grid, block, 0, ctx->stream, a);
     } else {
         wg_path(ctx, "gemv.n/t=%d,ns=%u", tile, nsplit);
-        if (tile == 1) hipLaunchKernelGGL((gemv_n_kernel<1, T>), grid, block, 0, ctx->stream, a);
-        else if (tile == 2) hipLaunchKernelGGL((gemv_n_kernel<2, T>), grid, block, 0, ctx->stream, a);
-        else if (tile == 4) hipLaunchKernelGGL((gemv_n_kernel<4, T>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((gemv_n_kernel<8, T>), grid, block, 0, ctx->stream, a);
+        typedef typename std::conditional<std::is_same<T, V>::value, T, MixedElems<T, V>>::type NE; // (gemv_n_kernel's one argument for the element types)
+#define WG_GEMV_N(NR) hipLaunchKernelGGL((gemv_n_kernel<NR, NE>), grid, block, 0, ctx->stream, a)
+        if (tile == 1) WG_GEMV_N(1);
+        else if (tile == 2) WG_GEMV_N(2);
+        else if (tile == 4) WG_GEMV_N(4);
+        else WG_GEMV_N(8);
+#undef WG_GEMV_N
     }
     WG_HIP_TRY(hipGetLastError());
     if (nsplit > 1) {
         wg_path(ctx, "gemv.combine/ns=%u", nsplit);
-        hipLaunchKernelGGL(gemv_combine_kernel<T>, dim3(ceil_div(rows_out / 4u, 4u), nrhs, nmats), block, 0, ctx->stream, a.part, nsplit, rows_out, nrhs, out,
+        hipLaunchKernelGGL(gemv_combine_kernel<V>, dim3(ceil_div(rows_out / 4u, 4u), nrhs, nmats), block, 0, ctx->stream, a.part, nsplit, rows_out, nrhs, out,
                            out_ld, out_batch);
         WG_HIP_TRY(hipGetLastError());
     }
@@ -966,6 +992,20 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
         return wgk_gemm_f32_skinny(ctx, trans, rows_out, nrhs, k, nmats, (float *)out, out_ld, out_batch, m, v, 1.f, 0.f);
     wg_path(ctx, "f32.gemv");
     return gemv_launch<float>(ctx, trans, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
+}
+
+// wg_gemv_mixed: a 16-bit matrix, f32 vectors and result. Always the Gemv kernels (the Gemm kernels of the 16-bit wgk_gemv would round v to 16 bits): more than
+// 8 right-hand sides run as groups of 8 in grid.z, one pass over the matrix per group.
+int wgk_gemv_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
+                   wgk_mat m, wgk_mat v) {
+    if (rows_out == 0 || nrhs == 0 || nmats == 0) return WG_OK;
+    wg_path(ctx, "gemv>");
+    if (m_dtype == WG_F16) {
+        wg_path(ctx, "f16w.gemv");
+        return gemv_launch<_Float16, float>(ctx, trans, rows_out, k, nrhs, nmats, out, out_ld, out_batch, m, v);
+    }
+    wg_path(ctx, "bf16w.gemv");
+    return gemv_launch<wg_bf16, float>(ctx, trans, rows_out, k, nrhs, nmats, out, out_ld, out_batch, m, v);
 }
 
 // One launch for result = reduce(op, m v) when the Gemv is launch-bound (the single-kernel shape family of wgk_gemv); WG_ERR_UNSUPPORTED

@@ -73,6 +73,21 @@ __device__ __forceinline__ void load_elems(uintptr_t base, uint32_t first, uint3
     }
 }
 
+// E entries of a vector of V elements beside a matrix whose lanes own E rows: the matrix's own type (one piece), or f32 beside a 16-bit matrix (wg_gemv_mixed:
+// a lane's 8 rows meet 8 f32 entries -- two 16-byte loads)
+template <typename V, int E, bool WHOLE>
+__device__ __forceinline__ void load_vec(uintptr_t base, uint32_t first, uint32_t len, float (&f)[E]) {
+    if constexpr (Elt<V>::E == E) load_elems<V, WHOLE>(base, first, len, f);
+    else {
+        static_assert(Elt<V>::E == 4 && E == 8, "f32 vectors beside a 16-bit matrix");
+        float lo[4], hi[4];
+        load_elems<V, WHOLE>(base, first, len, lo);
+        load_elems<V, WHOLE>(base, first + 4u, len, hi);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { f[e] = lo[e]; f[4 + e] = hi[e]; }
+    }
+}
+
 __device__ __forceinline__ float readlane_f(float x, uint32_t lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane)); }
 __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
@@ -81,7 +96,7 @@ __device__ __forceinline__ float wave_sum(float x) {
 }
 
 struct AnyArgs {
-    uintptr_t m; uint32_t ldm; uint64_t m_batch; // elements
+    uintptr_t m; uint32_t ldm; uint64_t m_batch; // elements (of each operand's own type: the matrix T, vectors and result V)
     uintptr_t v; uint32_t ldv; uint64_t v_batch;
     uintptr_t out; uint32_t ldo; uint64_t o_batch;
     float *part;       // f32 partials [matrix * rhs - zbase][split][out_len] when nsplit > 1 (the launch's own chunk of them)
@@ -97,7 +112,7 @@ __device__ __forceinline__ void store_out(const AnyArgs &a, uint32_t z, uint32_t
 }
 
 // grid = (row blocks of 64 E, column splits, matrices * right-hand sides)
-template <typename T, bool NT>
+template <typename T, bool NT, typename V = T>
 __global__ __launch_bounds__(kThreads) void gemv_any_n_kernel(AnyArgs a) {
     constexpr int E = Elt<T>::E, ES = Elt<T>::ES, U = WG_ANY_NU;
     __shared__ float part[kWaves][E][64];
@@ -108,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void gemv_any_n_kernel(AnyArgs a) {
     const uint32_t per_wave = (c_end - c_begin + kWaves - 1u) / kWaves;
     const uint32_t w_begin = min(c_end, c_begin + wave * per_wave), w_end = min(c_end, w_begin + per_wave);
     const uintptr_t mb = a.m + z * a.m_batch * ES;
-    const __attribute__((address_space(1))) T *vp = reinterpret_cast<const __attribute__((address_space(1))) T *>(a.v) + z * a.v_batch + (uint64_t)y * a.ldv;
+    const __attribute__((address_space(1))) V *vp = reinterpret_cast<const __attribute__((address_space(1))) V *>(a.v) + z * a.v_batch + (uint64_t)y * a.ldv;
     float acc[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) acc[e] = 0.f;
@@ -141,13 +156,13 @@ __global__ __launch_bounds__(kThreads) void gemv_any_n_kernel(AnyArgs a) {
 #pragma unroll
         for (int e = 0; e < E; ++e) {
             const float s = ((part[0][e][lane] + part[1][e][lane]) + part[2][e][lane]) + part[3][e][lane];
-            if (r0 + e < a.R) store_out<T>(a, z, y, blockIdx.y, a.R, r0 + e, s);
+            if (r0 + e < a.R) store_out<V>(a, z, y, blockIdx.y, a.R, r0 + e, s);
         }
     }
 }
 
 // grid = (groups of 4 * kWaves columns, row splits, matrices * right-hand sides)
-template <typename T, bool NT>
+template <typename T, bool NT, typename V = T>
 __global__ __launch_bounds__(kThreads) void gemv_any_t_kernel(AnyArgs a) {
     constexpr int E = Elt<T>::E, ES = Elt<T>::ES, CW = 4;
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -156,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void gemv_any_t_kernel(AnyArgs a) {
     if (c0 >= a.C) return;
     const uint32_t r_begin = blockIdx.y * a.per_split, r_end = min(a.R, r_begin + a.per_split);
     const uintptr_t mb = a.m + z * a.m_batch * ES;
-    const uintptr_t vb = a.v + (z * a.v_batch + (uint64_t)y * a.ldv) * ES;
+    const uintptr_t vb = a.v + (z * a.v_batch + (uint64_t)y * a.ldv) * Elt<V>::ES;
     float acc[CW];
 #pragma unroll
     for (int c = 0; c < CW; ++c) acc[c] = 0.f;
@@ -166,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void gemv_any_t_kernel(AnyArgs a) {
         float f[CW][E], x[E];
 #pragma unroll
         for (int c = 0; c < CW; ++c) load_elems<T, WHOLE, NT>(mb + (uint64_t)min(c0 + c, a.C - 1u) * a.ldm * ES, r0, r_end, f[c]);
-        load_elems<T, WHOLE>(vb, r0, r_end, x);
+        load_vec<V, E, WHOLE>(vb, r0, r_end, x);
 #pragma unroll
         for (int c = 0; c < CW; ++c)
 #pragma unroll
@@ -178,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void gemv_any_t_kernel(AnyArgs a) {
 #pragma unroll
     for (int c = 0; c < CW; ++c) {
         const float s = wave_sum(acc[c]);
-        if (lane == 0 && c0 + c < a.C) store_out<T>(a, z, y, blockIdx.y, a.C, c0 + c, s);
+        if (lane == 0 && c0 + c < a.C) store_out<V>(a, z, y, blockIdx.y, a.C, c0 + c, s);
     }
 }
 
@@ -193,7 +208,7 @@ __global__ __launch_bounds__(kThreads) void gemv_any_combine_kernel(AnyArgs a, u
     reinterpret_cast<T *>(a.out)[z * a.o_batch + (uint64_t)y * a.ldo + i] = (T)s;
 }
 
-template <typename T>
+template <typename T, typename V = T> // (V != T: wg_gemv_mixed -- splits, workgroups per CU and the non-temporal threshold follow the MATRIX's element size)
 int launch_any(wg_ctx *ctx, bool trans, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, void *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v) {
     constexpr uint32_t E = Elt<T>::E;
     const uint32_t cus = ctx->compute_units > 0 ? (uint32_t)ctx->compute_units : 256u;
@@ -231,13 +246,13 @@ int launch_any(wg_ctx *ctx, bool trans, uint32_t R, uint32_t C, uint32_t nrhs, u
         const uint32_t nz = gz - base < zchunk ? (uint32_t)(gz - base) : zchunk;
         const dim3 grid(gx, nsplit, nz), block(kThreads);
         if (trans) {
-            if (nt) hipLaunchKernelGGL((gemv_any_t_kernel<T, true>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((gemv_any_t_kernel<T, false>), grid, block, 0, ctx->stream, a);
-        } else if (nt) hipLaunchKernelGGL((gemv_any_n_kernel<T, true>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((gemv_any_n_kernel<T, false>), grid, block, 0, ctx->stream, a);
+            if (nt) hipLaunchKernelGGL((gemv_any_t_kernel<T, true, V>), grid, block, 0, ctx->stream, a);
+            else hipLaunchKernelGGL((gemv_any_t_kernel<T, false, V>), grid, block, 0, ctx->stream, a);
+        } else if (nt) hipLaunchKernelGGL((gemv_any_n_kernel<T, true, V>), grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((gemv_any_n_kernel<T, false, V>), grid, block, 0, ctx->stream, a);
         WG_HIP_TRY(hipGetLastError());
         if (nsplit > 1u) {
-            hipLaunchKernelGGL(gemv_any_combine_kernel<T>, dim3((out_len + kThreads - 1u) / kThreads, nz), block, 0, ctx->stream, a, out_len);
+            hipLaunchKernelGGL(gemv_any_combine_kernel<V>, dim3((out_len + kThreads - 1u) / kThreads, nz), block, 0, ctx->stream, a, out_len);
             WG_HIP_TRY(hipGetLastError());
         }
     }
@@ -253,4 +268,12 @@ int wgk_gemv_any(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t R, uint32_t C
     if (dtype == WG_F16) return launch_any<_Float16>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
     if (dtype == WG_BF16) return launch_any<wg_bf16>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
     return launch_any<float>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
+}
+
+// wg_gemv_mixed on a matrix view of any alignment: m holds m_dtype (f16 / bf16) elements, v and out f32
+int wgk_gemv_any_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
+                       wgk_mat m, wgk_mat v) {
+    if (R == 0 || C == 0 || nrhs == 0 || nmats == 0) return WG_OK;
+    if (m_dtype == WG_F16) return launch_any<_Float16, float>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
+    return launch_any<wg_bf16, float>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
 }

@@ -16,3 +16,31 @@
 //   3. above that bound the answer is 1 ("overlaps") whatever the truth, and *exact = 0.
 // `exact` may be NULL. Never answers 0 for footprints that intersect.
 int wg_views_overlap(const wg_view_shape &a, uint64_t byte_base_a, const wg_view_shape &b, uint64_t byte_base_b, uint32_t elem_size, int *exact);
+
+// Views of DIFFERENT element sizes (wg_gemv_mixed: an f32 `out` against a 16-bit matrix, possibly in one buffer): both are compared in 2-byte units. A column of r
+// f32 elements is one contiguous run of 2 r units, so the f32 view with rows, stride and stride_mat doubled -- and its offset folded into the byte base -- has the
+// same footprint as a view of 2-byte elements, and the exact comparison above applies with elem_size 2. A doubled field that no longer fits the 32 bits of
+// wg_view_shape (an f32 view of 2^31 rows and more, or strides that large where they count) leaves the intervals: disjoint intervals are disjoint footprints,
+// anything else is answered 1 with *exact = 0, like a pair past the run bound.
+inline int wg_views_overlap_f32_u16(const wg_view_shape &f32_view, uint64_t byte_base_f32, const wg_view_shape &u16_view, uint64_t byte_base_u16, int *exact) {
+    if (exact) *exact = 1;
+    const wg_view_shape &s = f32_view;
+    if (s.size[0] == 0 || s.size[1] == 0 || s.size[2] == 0) return 0;
+    const uint64_t rows = 2ull * s.size[0], stride = s.size[1] > 1 ? 2ull * s.stride : rows, stride_mat = s.size[2] > 1 ? 2ull * s.stride_mat : 0;
+    const uint64_t base = byte_base_f32 + 4ull * s.offset; // (a device address plus at most 16 GiB: no wrap)
+    if (rows <= 0xffffffffull && stride <= 0xffffffffull && stride_mat <= 0xffffffffull) {
+        const wg_view_shape scaled = { { (uint32_t)rows, s.size[1], s.size[2] }, (uint32_t)stride, (uint32_t)stride_mat, 0 };
+        return wg_views_overlap(scaled, base, u16_view, byte_base_u16, 2, exact);
+    }
+    // the intervals alone: each view as ONE dense column of its whole extent (extents in 128 bits; a view whose extent does not fit a column of 2^32 - 1 elements
+    // cannot be stated that way either and is answered conservatively)
+    typedef unsigned __int128 u128;
+    const u128 ext_f = (u128)(s.size[2] - 1) * s.stride_mat + (u128)(s.size[1] - 1) * s.stride + s.size[0]; // f32 elements from the first one on
+    const wg_view_shape &h = u16_view;
+    if (h.size[0] == 0 || h.size[1] == 0 || h.size[2] == 0) return 0;
+    const u128 ext_h = (u128)(h.size[2] - 1) * h.stride_mat + (u128)(h.size[1] - 1) * h.stride + h.size[0];
+    const u128 lo_f = base, hi_f = lo_f + 4 * ext_f, lo_h = (u128)byte_base_u16 + 2ull * h.offset, hi_h = lo_h + 2 * ext_h;
+    if (hi_f <= lo_h || hi_h <= lo_f) return 0;
+    if (exact) *exact = 0;
+    return 1;
+}

@@ -187,6 +187,13 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
 // Gemv / GemvTr on a matrix view of any alignment (gemv_any.hip): m is the R x C view as stored, v / out hold nrhs columns
 int wgk_gemv_any(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, void *out, uint32_t out_ld, uint64_t out_batch,
                  wgk_mat m, wgk_mat v);
+// mixed precision (wg_gemv_mixed): m holds m_dtype elements (WG_F16 / WG_BF16), v and out hold f32. The plan of the 16-bit wgk_gemv for the same shape, views and
+// context on the <16-bit matrix, f32 vectors> instances of the same kernels; never the Gemm kernels (they would round v). ld / batch strides count each
+// operand's own elements.
+int wgk_gemv_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats,
+                   float *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v);
+int wgk_gemv_any_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
+                       wgk_mat m, wgk_mat v);
 int wgk_gemv_small_reduce(wg_ctx *ctx, int op, uint32_t rows_out, uint32_t k, float *y, wgk_mat m, wgk_mat v, unsigned *counter, float *result);
 
 int wgk_gemm_f32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,

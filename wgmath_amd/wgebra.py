@@ -58,6 +58,15 @@ def _common_dtype(*views: GpuTensorView):
     return wg_dtype(dt)
 
 
+def _mixed_dtype(out: GpuTensorView, m: GpuTensorView, v: GpuTensorView) -> int:
+    """The matrix's wg_dtype of a mixed-precision call: `m` float16 / bfloat16 / float32, `v` and `out` float32 -- anything else is a TypeError."""
+    md = wg_dtype(m._tensor.dtype)
+    for name, x in (("v", v), ("out", out)):
+        if np.dtype(x._tensor.dtype) != np.dtype(np.float32):
+            raise TypeError(f"mixed-precision Gemv: `{name}` must be float32, got {x._tensor.dtype} (`m` carries the 16-bit type)")
+    return md
+
+
 def row_major_shader_defs() -> dict:
     """linalg/shape.rs:11-15: the shader definitions that switch `Shape` to row-major.  Pass them to `Gemm.from_device` /
     `Gemv.from_device` (the reference passes them to the shader composer) to get operators whose matrix views are row-major."""
@@ -129,6 +138,24 @@ class Gemv:
         check(fn(pass_._ctx.handle, int(variant), dt,
                  out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
                  v.buffer()._h, v.shape().to_c()))
+
+    def dispatch_mixed(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, v) -> None:
+        self.dispatch_mixed_generic(device, shapes, pass_, out, m, v, GemvVariant.Gemv)
+
+    def dispatch_mixed_tr(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, v) -> None:
+        self.dispatch_mixed_generic(device, shapes, pass_, out, m, v, GemvVariant.GemvTr)
+
+    def dispatch_mixed_generic(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, v, variant: GemvVariant) -> None:
+        """Extension (`wg_gemv_mixed`): a float16 / bfloat16 matrix with float32 vectors and a float32 result -- 16-bit weights, f32 activations. The matrix is
+        widened exactly, `v` is never narrowed, sums are f32 and the result is stored without a rounding step; a float32 matrix is `dispatch_generic`.
+        Column-major views only (the row-major surface has no mixed form)."""
+        out, m, v = as_view(out, 3), as_view(m, 3), as_view(v, 3)
+        md = _mixed_dtype(out, m, v)
+        if self.row_major:
+            raise TypeError("Gemv.dispatch_mixed*: the row-major operator surface has no mixed-precision form")
+        check(lib.wg_gemv_mixed(pass_._ctx.handle, int(variant), md,
+                                out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
+                                v.buffer()._h, v.shape().to_c()))
 
 
 def gemv_reduce(pass_: ComputePass, op: "ReduceOp", result: GpuTensor, m, v, variant: "GemvVariant" = None) -> None:
