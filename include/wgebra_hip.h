@@ -51,7 +51,7 @@ extern "C" {
 #endif
 
 #define WGEBRA_HIP_ABI_VERSION 5 /* 5: wg_debug_take_path; and the round-6 additions that came without a bump: wg_copy_view, wg_timestamps_reserve,
-                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE, wg_debug_gemm16_plan (an added diagnostic symbol with its two structs); WG_ERR_ALIASED = 9 (an appended status: calls that
+                                    wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE, wg_debug_gemm16_plan and wg_debug_gemm32_plan (added diagnostic symbols with their two structs each); WG_ERR_ALIASED = 9 (an appended status: calls that
                                     return it used to launch kernels that raced on their own operands) with wg_debug_views_overlap; and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
                                     that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump); wg_gemv_mixed (an added symbol);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
@@ -307,6 +307,43 @@ typedef struct wg_gemm16_plan {
  * slab reduce of a K cut included; for a padded call the pad tag followed by the inner call's tags. inner (may be NULL): the query of that inner call
  * (pad plans only; else a copy of `query`). Calibrated shares are planned from flat rates (the forced pattern, WG_TUNE_F16_BALANCE = 1, ignores them). */
 int wg_debug_gemm16_plan(const wg_gemm16_query *query, const char *prefix, wg_gemm16_plan *plan, char *tags, size_t cap, wg_gemm16_query *inner);
+/* The same for the f32 Gemm launcher (gemm32_plan.hip): "fill a wg_gemm32_query, ask the planner, do what the wg_gemm32_plan says". The f32 launcher reads no
+ * addresses: shapes, leading dimensions, matrix strides, the CU count and the four WG_TUNE_F32_* knobs decide everything. */
+typedef struct wg_gemm32_query {
+    uint32_t trans, M, N, K, nmats;          /* out (M x N) = op(m1) (M x K) * m2 (K x N); trans: m1 stored K x M */
+    uint32_t lda, ldb, ldc;                  /* leading dimensions of m1, m2 and out (elements) */
+    uint64_t a_batch, b_batch, c_batch;      /* matrix strides (elements) */
+    float alpha, beta;
+    uint32_t cus;                            /* compute units of the context's stream */
+    int32_t mid, mid_split, skinny, panels;  /* WG_TUNE_F32_MID, _MID_SPLIT, _SKINNY, _PANELS */
+} wg_gemm32_query;
+typedef enum wg_gemm32_leaf {
+    WG_GEMM32_NOTHING = 0,      /* an empty product: no launch, WG_OK */
+    WG_GEMM32_UNSUPPORTED = 1,  /* no launch: the call returns `status` with `message` */
+    WG_GEMM32_MID = 2,          /* the mid family (gemm_f32_mid.hip): bm x bn tiles, K cut across workgroups for nsplit > 1 */
+    WG_GEMM32_SKINNY = 3,       /* the few-column kernel (gemm_f32_skinny.hip), one panel */
+    WG_GEMM32_SKINNY_PANELS = 4,/* ... on 64-column panels */
+    WG_GEMM32_SKINNY_T = 5,     /* ... computing the transposed product of a few-row one, written straight into the transposed position */
+    WG_GEMM32_FEWROW = 6,       /* the few-row form on transposed copies: C^T = m2^T op(m1)^T as a GemmTr (the inner call), then a transpose of the result */
+    WG_GEMM32_BIG = 7           /* 256 x 128 tiles (gemm_f32.hip): one launch, split-K slabs, or full rounds + a cut-up tail */
+} wg_gemm32_leaf;
+typedef struct wg_gemm32_plan {
+    uint32_t leaf;                           /* wg_gemm32_leaf */
+    uint32_t bm, bn;                         /* WG_GEMM32_MID: the tile */
+    uint32_t nsplit, k_per_split;            /* K cut (1, K: none), final: no empty split; every split but the last covers k_per_split */
+    uint32_t npanels;                        /* the few-column kernels: 64-column panels (1: none) */
+    uint32_t copy_a;                         /* WG_GEMM32_FEWROW: op(m1) is copied transposed (Gemm; GemmTr's m1 is used where it lies) */
+    uint32_t tail_r, tail_sp, tail_kps;      /* WG_GEMM32_BIG: tail tiles cut along K (0: none), their splits (final) and k per split */
+    uint32_t flat_tiles;                     /* ... the tail split of a batch: tiles per matrix, the launches number the tiles through the batch (0: grid.y carries the matrix) */
+    uint64_t workspace_bytes;                /* split-K slabs or tail partials (the context's workspace) */
+    uint64_t pad_workspace_bytes;            /* WG_GEMM32_FEWROW: the transposed copy of op(m1) and the transposed result (the context's padding workspace) */
+    int32_t status;                          /* WG_GEMM32_NOTHING / _UNSUPPORTED */
+    char message[128];
+} wg_gemm32_plan;
+/* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the slab reduce of a K cut included; for a
+ * few-row plan the tag string goes on with the transposes and the inner call's tags. inner (may be NULL): the query of that inner call (few-row plans only; else a
+ * copy of `query`). */
+int wg_debug_gemm32_plan(const wg_gemm32_query *query, wg_gemm32_plan *plan, char *tags, size_t cap, wg_gemm32_query *inner);
 int wg_ctx_get_tuning(const wg_ctx *ctx, wg_tuning key, int *value);
 /* Diagnostics / tests (no context, no device): the predicate behind WG_ERR_ALIASED. Returns 1 when the footprints of two views share a byte, 0 when they do not.
  * byte_base_*: the byte address of element 0 of the buffer each view indexes (wg_buf_device_ptr; any integers do, only their difference matters); elem_size: bytes

@@ -22,7 +22,8 @@ def test_library_exports_every_declared_symbol_at_abi_5():
     assert not missing, f"include/wgebra_hip.h declares symbols the library does not export: {missing}"
     assert set(declared) == set(_lib.lib._wg_signatures), "the ctypes binding and the header disagree on the entry points"
     # 3: the SDMA rect-copy exchange engine is gone (gather mode 1, wg_comm_copy_engine, peer_out), + wg_comm_reported_size, wg_debug_clock_*, wg_debug_mfma_ceiling; 5: wg_debug_take_path
-    # (added since without a bump, as the round-6 additions were: wg_debug_gemm16_plan -- tests/test_gemm16_plan_host.py; wg_debug_views_overlap with the
+    # (added since without a bump, as the round-6 additions were: wg_debug_gemm16_plan -- tests/test_gemm16_plan_host.py; wg_debug_gemm32_plan --
+    # tests/test_gemm32_plan_host.py; wg_debug_views_overlap with the
     # appended status WG_ERR_ALIASED -- tests/test_operand_overlap.py)
     hdr = open(_lib.HEADER_PATH).read()
     assert _lib.lib.wg_abi_version() == _lib.ABI_VERSION == 5 and f"#define WGEBRA_HIP_ABI_VERSION {_lib.ABI_VERSION} " in hdr

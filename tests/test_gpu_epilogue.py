@@ -11,6 +11,9 @@ move a row to another leaf. Per row, variant and output view (dense; odd offset,
      rerouted calls within |alpha| gate + an ulp of |alpha truth| + |beta C0| of the f64 value; the log shows the leaf (or reroute) the row expects;
   5. everything around and between the output's columns and matrices is bit-unchanged (a sentinel NaN pattern).
 """
+import ctypes
+import itertools
+
 import numpy as np
 import pytest
 
@@ -94,9 +97,12 @@ def knobs(gpu):
     """Sets a row's knobs (wg_ctx_set_tuning) and restores them afterwards, as tests/test_gpu_parity.py's f16_tile does."""
     saved = {}
 
-    def set_(d):
+    def set_(d, inst=None):
         for k, v in d.items():
-            saved.setdefault(k, gpu.set_tuning(k, v))
+            if inst is None or inst is gpu:
+                saved.setdefault(k, gpu.set_tuning(k, v))
+            else:  # (a context of the test's own: restored, or closed, by the test)
+                inst.set_tuning(k, v)
 
     yield set_
     for k, v in saved.items():
@@ -238,6 +244,85 @@ def test_epilogue_leaf(gpu, knobs, row, tr, record_property):
             assert (err <= tol).all(), f"gemm_ex({alpha}, {beta}) {view} [{log4}]: worst err/tol {(err / tol).max():.3g}"
     record_property("leaf_logs", " | ".join(logs))
     print(f"\n{row.name} {'tr' if tr else 'nn'}: " + " | ".join(logs))
+
+
+# --------------------------------------------------------------------------------------------------------
+# The f32 launcher executes its plan (gemm32_plan.hip): the real launch log is the planner's, leaf by leaf
+# --------------------------------------------------------------------------------------------------------
+def _plan32(tr, M, K, N, mats, cus, knobs):
+    """(plan, tags) of wg_debug_gemm32_plan for the product on dense views."""
+    L = _lib()
+    q, p, buf = L.Gemm32QueryC(), L.Gemm32PlanC(), ctypes.create_string_buffer(256)
+    q.trans, q.M, q.N, q.K, q.nmats = int(tr), M, N, K, mats
+    q.lda, q.ldb, q.ldc = (K if tr else M), K, M
+    q.a_batch, q.b_batch, q.c_batch = M * K, K * N, M * N
+    q.alpha, q.beta, q.cus = 1.0, 0.0, cus
+    q.mid, q.mid_split, q.skinny, q.panels = knobs
+    L.check(L.lib.wg_debug_gemm32_plan(ctypes.byref(q), ctypes.byref(p), buf, len(buf), None))
+    return p, buf.value.decode()
+
+
+F32_KNOBS = ("f32_mid", "f32_mid_split", "f32_skinny", "f32_panels")
+# the context's defaults first; then, as the rows of LEAVES do, the mid family and the panels off (the 256 x 128 tiles on products of a test's size) and the panels forced
+F32_KNOB_SETS = ((-1, 0, -1, -1), (0, 0, -1, 0), (-1, 0, -1, 1))
+
+
+def _smallest_query_per_leaf(cus):
+    """kind of plan -> (knobs, variant, M, K, N, matrices, tags): for every leaf of the f32 launcher -- and, within a leaf, with and without a K cut, a cut-up tail, a
+    copy of op(m1) -- the smallest product (by M N K matrices, below 2^33 flop) of a grid of sizes that the planner sends there on `cus` compute units."""
+    L, best = _lib(), {}
+    sizes = (4, 16, 32, 48, 64, 96, 128, 256, 512, 1024, 2048, 4096, 4352, 8192)
+    for knobs, tr, mats, M, N, K in itertools.product(F32_KNOB_SETS, (False, True), (1, 4), sizes, sizes, (32, 128, 256, 512, 1024, 4096)):
+        if 2 * M * N * K * mats >= 2 ** 33:
+            continue
+        p, log = _plan32(tr, M, K, N, mats, cus, knobs)
+        leaf = L.GEMM32_LEAVES[p.leaf]
+        if leaf in ("nothing", "unsupported"):
+            continue
+        kind, size = (leaf, p.nsplit > 1, p.tail_r > 0, bool(p.copy_a)), M * N * K * mats
+        if kind not in best or size < best[kind][0]:
+            best[kind] = (size, knobs, tr, M, K, N, mats, log)
+    return {k: v[1:] for k, v in best.items()}
+
+
+def test_f32_executor_logs_its_plan(gpu, knobs):
+    """The smallest product the planner sends to each leaf, on the whole chip and on 8 CUs: the launch log is exactly wg_debug_gemm32_plan's tags (with
+    tests/test_gemm32_plan_host.py, which holds the planner to the launcher it replaced, this pins the executor to the plan), and the result is the f64 product
+    within the file's f32 bound."""
+    wg = _wg()
+    small = wg.GpuInstance.new(0, cu_count=8)
+    try:
+        for cus, inst in ((int(gpu.adapter()["compute_units"]), gpu), (8, small)):
+            found = _smallest_query_per_leaf(cus)
+            assert {k[0] for k in found} == {"mid", "skinny", "skinny_panels", "skinny_t", "fewrow", "big"}, sorted(found)
+            assert len(found) >= 10, sorted(found)
+            inst.take_path()
+            for kind, (kn, tr, M, K, N, mats, want) in sorted(found.items()):
+                knobs(dict(zip(F32_KNOBS, kn)), inst)
+                rng = np.random.default_rng(M * 7 + K * 5 + N * 3 + mats + int(tr))
+                a = rng.random((mats, M * K), dtype=np.float32) * 2 - 1
+                b = rng.random((mats, K * N), dtype=np.float32) * 2 - 1
+                ta, tb = _upload(inst, a.ravel()), _upload(inst, b.ravel())
+                ash = wg.ViewShape(((K, M) if tr else (M, K)) + (mats,), K if tr else M, M * K, 0)
+                bsh = wg.ViewShape((K, N, mats), K, K * N, 0)
+                out = OutView(inst, F32, M, N, mats, dense=True)
+                out.fill(np.full((M, N, mats), np.nan, F32))
+                _gemm(inst, tr, F32, out, ta, ash, tb, bsh)
+                log = inst.take_path()
+                what = f"{kind} {'tr' if tr else 'nn'} {M} x {K} x {N} x {mats} on {cus} CUs"
+                assert log == want, f"{what}: the plan logs {want!r}, the launch {log!r}"
+                R = out.read(what).astype(np.float64)
+                for z in range(mats):
+                    A = a[z].astype(np.float64).reshape((M, K) if tr else (K, M))
+                    A = A if tr else A.T  # (column-major K x M read row-major is op(A); column-major M x K read row-major is its transpose)
+                    B = b[z].astype(np.float64).reshape((N, K)).T
+                    err, gate = np.abs(R[:, :, z] - A @ B), U.f32_gate(K, np.abs(A) @ np.abs(B))
+                    assert (err <= gate).all(), f"{what} [{log}]: worst err/tol {(err / gate).max():.3g}"
+    finally:
+        for k, v in zip(F32_KNOBS, F32_KNOB_SETS[0]):
+            small.set_tuning(k, v)
+        small.sync()
+        small.close()
 
 
 # --------------------------------------------------------------------------------------------------------

@@ -55,6 +55,24 @@ class Gemm16PlanC(ctypes.Structure):
                 + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
 
 
+class Gemm32QueryC(ctypes.Structure):
+    """wg_gemm32_query: everything the f32 Gemm launcher's choice of kernels depends on (wg_debug_gemm32_plan)."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("trans", "M", "N", "K", "nmats", "lda", "ldb", "ldc")]
+                + [(n, ctypes.c_uint64) for n in ("a_batch", "b_batch", "c_batch")]
+                + [("alpha", ctypes.c_float), ("beta", ctypes.c_float), ("cus", ctypes.c_uint32)]
+                + [(n, ctypes.c_int32) for n in ("mid", "mid_split", "skinny", "panels")])
+
+
+GEMM32_LEAVES = ("nothing", "unsupported", "mid", "skinny", "skinny_panels", "skinny_t", "fewrow", "big")  # wg_gemm32_leaf
+
+
+class Gemm32PlanC(ctypes.Structure):
+    """wg_gemm32_plan: the leaf (index into GEMM32_LEAVES) and what it is launched with."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("leaf", "bm", "bn", "nsplit", "k_per_split", "npanels", "copy_a", "tail_r", "tail_sp", "tail_kps", "flat_tiles")]
+                + [("workspace_bytes", ctypes.c_uint64), ("pad_workspace_bytes", ctypes.c_uint64)]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
+
+
 class WgError(RuntimeError):
     """A non-OK wg_status.  `.status` is the code, the message is wg_last_error_string()."""
 
@@ -119,6 +137,7 @@ def _load() -> ctypes.CDLL:
         "wg_ctx_reserve_workspace": (ci, [vp, sz]),
         "wg_debug_f16_balance_plan": (ci, [ctypes.POINTER(ctypes.c_double), u32, u32, ci, ctypes.POINTER(u32), u32, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "wg_debug_gemm16_plan": (ci, [ctypes.POINTER(Gemm16QueryC), cp, ctypes.POINTER(Gemm16PlanC), cp, sz, ctypes.POINTER(Gemm16QueryC)]),
+        "wg_debug_gemm32_plan": (ci, [ctypes.POINTER(Gemm32QueryC), ctypes.POINTER(Gemm32PlanC), cp, sz, ctypes.POINTER(Gemm32QueryC)]),
         "wg_ctx_f16_balance_info": (ci, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ci), ctypes.POINTER(u32), ctypes.POINTER(u32)]),
         "wg_debug_views_overlap": (ci, [S, u64, S, u64, u32, ctypes.POINTER(ci)]),
         "wg_debug_take_path": (ci, [vp, cp, sz]),

@@ -3,6 +3,7 @@
 // call, no context -- the launcher (gemm_f16.hip) executes the plan, tests read it through wg_debug_gemm16_plan and tests/cpp/gemm16_plan_check.cpp links this
 // unit alone (under the host sanitizers).
 #include "gemm16_plan.hpp"
+#include "gemm_plan_common.hpp" // wg_splitk_plan, the slab cost and the few-column K cut, shared with gemm32_plan.hip
 
 #include <cmath>
 #include <cstdarg>
@@ -15,17 +16,6 @@ using WG16_NS::BM; // (tile constants of the 16-bit kernels: the same in both bu
 using WG16_NS::BN;
 using WG16_NS::BKH;
 using WG16_NS::kPanelTail;
-
-// How many K-splits to use (1 = none). `tiles` = output tiles x matrices, `slots` = workgroups the chip holds at once,
-// `k_units` = K / (kernel's K granule), `min_units` = fewest granules worth a workgroup's prologue/epilogue. (Shared with gemm_f32.hip.)
-uint32_t wg_splitk_plan(uint64_t tiles, uint32_t slots, uint32_t k_units, uint32_t min_units, uint64_t out_elems, uint64_t max_ws_bytes) {
-    if (tiles == 0 || tiles * 2 > slots) return 1; // at least half the chip is busy already
-    uint32_t s = (uint32_t)(slots / tiles);
-    const uint32_t by_k = k_units / min_units;
-    if (s > by_k) s = by_k;
-    while (s > 1 && (uint64_t)s * out_elems * 4u > max_ws_bytes) --s;
-    return s < 2 ? 1 : s;
-}
 
 namespace {
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -154,20 +144,10 @@ wg_gemm16_plan gemm16_plan(const wg_gemm16_query &q) {
     if (WG_F16_SKINNY && trans && !panels && N <= 16u && M >= 512u && M % 4u == 0 && K >= 256u && K % 8u == 0 && m1.ld % 8u == 0 && m2.ld % 8u == 0 &&
         out_ld % 4u == 0 && al16(m1.addr) && al16(m2.addr) && (q.c_addr & 7) == 0 && (nmats == 1 || (m1.batch % 8u == 0 && m2.batch % 8u == 0 && out_batch % 4u == 0)) &&
         (uint64_t)M * K * 2u >= (16ull << 20) && (uint64_t)m1.ld * 32u * 2u < (1ull << 31) && (uint64_t)m2.ld * 32u * 2u < (1ull << 31)) {
-        // its K cut: the split with the fewest rounds x (K / c + 256)
+        // its K cut: the split with the fewest rounds x (K / c + 256) -- the f32 launcher's plan at 64 k per stage, >= 256 k (4 stages) per workgroup
         const uint32_t row_blocks = (M + 127u) / 128u;
-        const uint32_t max_split = (K + 255u) / 256u; // >= 256 k (4 stages) per workgroup
-        const uint64_t blocks = (uint64_t)row_blocks * nmats;
-        uint32_t ns = 1;
-        uint64_t best = ~0ull;
-        for (uint32_t c = 1; c <= max_split && (uint64_t)c * blocks <= 4ull * cus + blocks; ++c) { // the f32 launcher's plan at 64 k per stage
-            if ((uint64_t)c * M * N * nmats * 4u > (512ull << 20)) break;
-            const uint64_t rounds = (blocks * c + cus - 1) / cus;
-            const uint64_t cost = rounds * ((K + c - 1) / c + 256u);
-            if (cost < best) { best = cost; ns = c; }
-        }
-        uint32_t kps = (((K + ns - 1) / ns) + 63u) & ~63u;
-        ns = (K + kps - 1) / kps;
+        uint32_t kps;
+        const uint32_t ns = wg_skinny_kcut(M, N, K, nmats, (uint64_t)row_blocks * nmats, (uint64_t)cus, 256u, 64u, 0, &kps);
         if (ns > 65535u || nmats > 65535u) return no_launch(p, WG_ERR_UNSUPPORTED, "Gemm: too many splits or matrices for the skinny path");
         p.leaf = WG_GEMM16_SKINNY;
         p.tiles_m = row_blocks; p.tiles_n = 1;
@@ -259,7 +239,7 @@ wg_gemm16_plan gemm16_plan(const wg_gemm16_query &q) {
         }
         if ((krem == 0 || K - krem >= 64u) && !panels) {
             const double out_bytes = (double)M * N * nmats * 4.0;
-            auto slabs = [&](uint32_t ns) { return ns > 1 ? ns * out_bytes / 3.5e6 + 3.0 + 4.0 + ns * out_bytes / 7.0e6 : 0.0; };
+            auto slabs = [&](uint32_t ns) { return ns > 1 ? wg_slab_write_us(ns * out_bytes) + wg_slab_reduce_us(ns * out_bytes) : 0.0; };
             const uint32_t tm = (M + 127u) / 128u, tn = (N + 127u) / 128u;
             const uint64_t tiles128 = (uint64_t)tm * tn;
             // split-K only when even these tiles leave more than half of the CUs empty, and then >= 1024 k per split

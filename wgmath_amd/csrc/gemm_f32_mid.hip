@@ -20,6 +20,7 @@
 // Ragged M / N: DMA rows past the end are clamped to the last valid one, their results never stored. K % 16 != 0 (a multiple of 4 by the
 // operator's precondition): one more k-tile after the pipelined loop, staged through registers with the missing k zero-filled.
 #include "wg_internal.hpp"
+#include "gemm32_plan.hpp"
 
 #include <type_traits>
 
@@ -578,43 +579,29 @@ int launch(wg_ctx *ctx, bool trans, uint32_t nmats, const MidArgs &g) {
 
 } // namespace
 
-bool wgk_gemm_f32_mid_ok(uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wgk_mat m1, wgk_mat m2) {
-    // at least one whole k-tile of either family; 32-bit byte offsets inside a tile's 128 rows / 16 k-rows; grid.y
-    return K >= 32 && K % 4 == 0 && M >= 4 && N >= 4 && nmats <= 65535 && (uint64_t)m1.ld * 128u * 4u < (1ull << 31) && (uint64_t)m2.ld * 128u * 4u < (1ull << 31);
-}
-
-int wgk_gemm_f32_mid(wg_ctx *ctx, bool trans, int bm, int bn, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
-                     wgk_mat m1, wgk_mat m2, float alpha, float beta, uint32_t nsplit) {
-    const bool kw = !(bm == 128 || bn == 128);
-    if (nsplit > 1 && !kw) nsplit = 1; // (the 2 x 2-wave tiles have no split form)
-    uint32_t kps = K;
-    for (uint32_t want = nsplit; nsplit > 1; --want) { // whole k-tiles per split, no empty split, at least one whole k-tile in the last one
-        if (want <= 1) { nsplit = 1; kps = K; break; }
-        kps = (((K + 31u) / 32u + want - 1u) / want) * 32u;
-        const uint32_t n = (K + kps - 1u) / kps;
-        if (n > 1 && K - (n - 1u) * kps >= 32u) { nsplit = n; break; }
-    }
-    if ((uint64_t)nmats * nsplit > 65535u) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: nmats * splits exceeds 65535");
+// Launch only: the tile and the K cut -- p.nsplit splits of p.k_per_split, whole k-tiles, no empty split -- are the caller's plan (gemm32_plan.hip)
+int wgk_gemm_f32_mid(wg_ctx *ctx, const wg_gemm32_plan &p, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
+                     wgk_mat m1, wgk_mat m2, float alpha, float beta) {
+    const int bm = (int)p.bm, bn = (int)p.bn;
     MidArgs g;
     g.a = (const float *)m1.ptr; g.lda = m1.ld; g.a_batch = m1.batch;
     g.b = (const float *)m2.ptr; g.ldb = m2.ld; g.b_batch = m2.batch;
     g.c = out; g.ldc = out_ld; g.c_batch = out_batch;
     g.M = M; g.N = N; g.K = K;
     g.alpha = alpha; g.beta = beta;
-    g.nsplit = nsplit > 1 ? nsplit : 1u; g.k_per_split = kps;
+    g.nsplit = p.nsplit; g.k_per_split = p.k_per_split;
     float *part = nullptr;
     if (g.nsplit > 1) { // raw partial sums into f32 slabs; alpha / beta are applied by the ordered reduce
         void *ws = nullptr;
-        if (int rc = wg_ctx_workspace(ctx, (size_t)g.nsplit * M * N * nmats * sizeof(float), &ws)) return rc;
+        if (int rc = wg_ctx_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
         part = (float *)ws;
         g.c = part; g.ldc = M; g.c_batch = (uint64_t)M * N;
         g.alpha = 1.f; g.beta = 0.f;
     }
     g.tiles_m = (M + (uint32_t)bm - 1) / (uint32_t)bm;
     g.tiles_n = (N + (uint32_t)bn - 1) / (uint32_t)bn;
-    if ((uint64_t)g.tiles_m * g.tiles_n > 0x7fffffffull) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: too many tiles");
     int rc = WG_ERR_INVALID_ARG;
-    wg_path(ctx, "f32.mid%dx%d/ns=%u", bm, bn, g.nsplit);
+    wg_path(ctx, "%s", gemm32_tags(p).tag[0]);
     if (bm == 128 && bn == 128) rc = launch<2, 2>(ctx, trans, nmats, g);
     else if (bm == 128 && bn == 64) rc = launch<2, 1>(ctx, trans, nmats, g);
     else if (bm == 64 && bn == 128) rc = launch<1, 2>(ctx, trans, nmats, g);

@@ -12,6 +12,7 @@
 // stage was 50-70 % slower (the waves drift with memory latency); a 16-wide MFMA variant for N <= 16 changed nothing THEN (round 1, a slower stream) and is
 // the shipped form for N <= 16 since round 5 (W16 below): with the stream at 5.3 TB/s the 32-wide MFMAs kept the matrix pipe busy 58 % of the time and the clock at 1.9 GHz.
 #include "wg_internal.hpp"
+#include "gemm32_plan.hpp"
 #include "gemm_f16_common.hpp" // the 16-bit element-type switch (the T = 16-bit instance)
 #include <cstdlib>
 #include <type_traits>
@@ -401,35 +402,14 @@ __global__ __launch_bounds__(256, 1) void WG_SKINNY_KERNEL16(SkinnyArgs g) {
 } // namespace
 
 #ifndef WG_GEMM16_BF16
-// out = alpha * m1 * m2 + beta * out for N <= 64 (NN only). Returns WG_ERR_UNSUPPORTED-free: the caller checks applicability.
-int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
-                        wgk_mat m1, wgk_mat m2, float alpha, float beta, uint32_t out_row_stride, bool m2_kmajor, uint32_t ns_force) {
-    const int cus = ctx->compute_units > 0 ? ctx->compute_units : 256;
-    const uint32_t row_blocks = (M + 127u) / 128u;
-    // K splits: the count whose workgroups fill whole rounds of the CUs with the least k per round (11008 rows = 86 row blocks: 3 splits
-    // = 258 workgroups would run a second round for two of them; 5 splits = 430 run two rounds of 820 k). Measured: one long workgroup
-    // per CU beats several short ones (4096 x 16 x 4096: 24 us with 256 workgroups, 32 us with 1024), so ties go to fewer splits and
-    // every extra split is charged the k-equivalent of its slab + epilogue.
-    const uint32_t max_split = (K + 127u) / 128u; // >= 128 k per workgroup
-    // more than 64 columns (small squares, see wgk_gemm_f32): 64-column panels over grid.z, every panel streaming A from L2
-    const uint32_t npanels = N > 64u ? (N + 63u) / 64u : 1u;
-    if ((uint64_t)nmats * npanels > 65535u) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: too many matrices x column panels");
-    const uint64_t blocks = (uint64_t)row_blocks * nmats * npanels;
-    uint32_t ns = 1;
-    uint64_t best = ~0ull;
-    for (uint32_t c = 1; c <= max_split && (uint64_t)c * blocks <= 4ull * cus + blocks; ++c) {
-        if ((uint64_t)c * M * N * nmats * 4u > (512ull << 20)) break;
-        const uint64_t rounds = (blocks * c + cus - 1) / cus;
-        const uint64_t cost = rounds * ((K + c - 1) / c + 128u); // + pipeline fill, epilogue and slab per round (11008 x 32 x 4096: 5 splits 49 us, 11 splits 52)
-        if (cost < best) { best = cost; ns = c; }
-    }
-    if (ns_force) ns = ns_force > max_split ? max_split : ns_force;
-    uint32_t kps = (((K + ns - 1) / ns) + 31u) & ~31u;
-    ns = (K + kps - 1) / kps;
-    if (ns > 65535u || nmats > 65535u) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: too many splits or matrices for the skinny path");
+// out = alpha * op(m1) * m2 + beta * out on the few-column kernel. Launch only: the caller's plan (gemm32_plan.hip: gemm32_plan / gemm32_skinny_plan) has checked
+// applicability and chose the panels and the K cut -- p.nsplit splits of p.k_per_split; the f32 slabs and their reduce are this function's.
+int wgk_gemm_f32_skinny(wg_ctx *ctx, const wg_gemm32_plan &p, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
+                        wgk_mat m1, wgk_mat m2, float alpha, float beta, uint32_t out_row_stride, bool m2_kmajor) {
+    const uint32_t row_blocks = (M + 127u) / 128u, npanels = p.npanels, ns = p.nsplit, kps = p.k_per_split;
     void *ws = nullptr;
     if (ns > 1)
-        if (int rc = wg_ctx_workspace(ctx, (size_t)ns * M * N * nmats * sizeof(float), &ws)) return rc;
+        if (int rc = wg_ctx_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
     SkinnyArgs g;
     g.c = out; g.ldc = out_ld; g.c_batch = out_batch; g.alpha = alpha; g.beta = beta; g.crs = out_row_stride;
     g.a = (const float *)m1.ptr; g.lda = m1.ld; g.a_batch = m1.batch;
@@ -439,8 +419,7 @@ int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_
     g.a_nt = (npanels == 1 && (uint64_t)M * K * 4u >= (384ull << 20)) ? 1u : 0u; // read once, and no use to the 256 MiB Infinity Cache (tr_dma_streamed)
     const dim3 grid(row_blocks, ns, nmats * npanels);
     const bool w16 = WG_SKINNY_W16 && N <= 16u && npanels == 1u;
-    if (npanels > 1u) wg_path(ctx, "f32.skinny%s/p=%u,ns=%u", m2_kmajor || out_row_stride != 1u ? "T" : "", npanels, ns);
-    else wg_path(ctx, "f32.skinny%s/ns=%u", m2_kmajor || out_row_stride != 1u ? "T" : "", ns);
+    wg_path(ctx, "%s", gemm32_tags(p).tag[0]);
     if (m2_kmajor) { // GemmTr only (the few-row route)
         if (w16) hipLaunchKernelGGL((gemm_f32_skinny_kernel<true, 1, true, true>), grid, dim3(256), 0, ctx->stream, g);
         else if (N <= 32) hipLaunchKernelGGL((gemm_f32_skinny_kernel<true, 1, true>), grid, dim3(256), 0, ctx->stream, g);

@@ -20,6 +20,7 @@
 // parity is tolerance-based: the order here is "per-lane sequential, then butterfly", which satisfies the
 // same error bound as both WGSL orders.
 #include "wg_internal.hpp"
+#include "gemm32_plan.hpp"
 #include "reduce_ops.hpp"
 #include <cstdlib>
 #include <type_traits>
@@ -751,7 +752,7 @@ static bool uses_small_kernel(int cus, bool trans, uint32_t rows_out, uint32_t k
 template <typename T, typename V = T>
 static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, V *out, uint32_t out_ld, uint64_t out_batch,
                        wgk_mat m, wgk_mat v) {
-    const int cus = ctx->compute_units > 0 ? ctx->compute_units : 256;
+    const int cus = wg_ctx_cus(ctx);
     const uint32_t rhs_groups = ceil_div(nrhs, kMaxRhs);
     const uint64_t gz64 = (uint64_t)nmats * rhs_groups;
     if (gz64 > 65535) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemv: nmats * ceil(nrhs/8) = %llu exceeds 65535", (unsigned long long)gz64);
@@ -911,7 +912,7 @@ static int gemv_t_lds_launch(wg_ctx *ctx, uint32_t rows_out, uint32_t k, uint32_
     a.rows_out = rows_out; a.k = k; a.nrhs = nrhs; a.k_per_split = k;
     a.out = out; a.part = nullptr; a.ld_dst = out_ld; a.dst_split = 0; a.dst_batch = out_batch;
     const int tile = nrhs > 4 ? 8 : (nrhs > 2 ? 4 : 2);
-    const uint32_t cus = (uint32_t)(ctx->compute_units > 0 ? ctx->compute_units : 256);
+    const uint32_t cus = (uint32_t)wg_ctx_cus(ctx);
     const TLdsPlan pl = gemv_t_lds_plan(cus, rows_out, k, (uint32_t)tile);
     const dim3 grid(pl.grid, 1, nmats);
     wg_path(ctx, "gemv.tlds/nr=%d,c=%d,th=%d", tile, pl.cols, pl.threads);
@@ -951,7 +952,7 @@ static bool uses_t_lds(const wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_
     if (!WG_GEMVT_LDS || !trans || es != 4u || nrhs < 2u || nrhs > 8u || nmats > 65535u) return false;
     if (!ctx->tuning[WG_TUNE_GEMVT_LDS] && uses_t_cols2<float>(trans, nrhs, rows_out, k)) return false; // (two right-hand sides on the column kernel's 2-vector form)
     const uint32_t forced = (uint32_t)ctx->tuning[WG_TUNE_GEMVT_LDS], min_cols = forced ? forced : 128u; // (forced: tests, experiments -- wg_ctx_set_tuning)
-    const uint32_t cus = (uint32_t)(ctx->compute_units > 0 ? ctx->compute_units : 256);
+    const uint32_t cus = (uint32_t)wg_ctx_cus(ctx);
     const uint32_t tile = nrhs > 4u ? 8u : (nrhs > 2u ? 4u : 2u);
     if (rows_out % 4u || k % 4u || k < 128u) return false;
     const bool whole = (uint64_t)k * tile * 4u <= (128u << 10);                       // one chunk: staged once per workgroup
@@ -988,8 +989,11 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
     // 9 .. 64 right-hand sides are a Gemm with few columns: one pass over the matrix on the matrix cores (gemm_f32_skinny.hip) instead of
     // one GEMV pass per 8 columns. (The 32-bit DMA offsets of that kernel must suffice for both operands, in both variants.)
     if ((nrhs > (uint32_t)kMaxRhs || few_rhs_as_gemm(trans, false, rows_out, k, nrhs, 4u)) && nrhs <= 64u && rows_out >= 512u && k >= 128u &&
-        (uint64_t)m.ld * 32u * 4u < (1ull << 31) && (uint64_t)v.ld * 64u * 4u < (1ull << 31))
-        return wgk_gemm_f32_skinny(ctx, trans, rows_out, nrhs, k, nmats, (float *)out, out_ld, out_batch, m, v, 1.f, 0.f);
+        (uint64_t)m.ld * 32u * 4u < (1ull << 31) && (uint64_t)v.ld * 64u * 4u < (1ull << 31)) {
+        const wg_gemm32_plan p = gemm32_skinny_plan(rows_out, nrhs, k, nmats, (uint32_t)wg_ctx_cus(ctx)); // its K cut
+        if (p.leaf == WG_GEMM32_UNSUPPORTED) return wg_set_error(p.status, "%s", p.message);
+        return wgk_gemm_f32_skinny(ctx, p, trans, rows_out, nrhs, k, nmats, (float *)out, out_ld, out_batch, m, v, 1.f, 0.f);
+    }
     wg_path(ctx, "f32.gemv");
     return gemv_launch<float>(ctx, trans, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
 }
@@ -1011,7 +1015,7 @@ int wgk_gemv_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t rows_out,
 // One launch for result = reduce(op, m v) when the Gemv is launch-bound (the single-kernel shape family of wgk_gemv); WG_ERR_UNSUPPORTED
 // tells the caller to run Gemv and Reduce as two launches. `y` is a scratch vector of rows_out floats, `counter` a zeroed device word.
 int wgk_gemv_small_reduce(wg_ctx *ctx, int op, uint32_t rows_out, uint32_t k, float *y, wgk_mat m, wgk_mat v, unsigned *counter, float *result) {
-    const int cus = ctx->compute_units > 0 ? ctx->compute_units : 256;
+    const int cus = wg_ctx_cus(ctx);
     if (k < 4u || !uses_small_kernel(cus, false, rows_out, k, 1, plan_nsplit<float>(cus, false, rows_out, k, 1, 1, m.ld))) return WG_ERR_UNSUPPORTED;
     GemvArgs a;
     a.m = (const float *)m.ptr; a.ldm = m.ld; a.m_batch = 0;

@@ -60,7 +60,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_strided_kernel(const float 
 
 } // namespace
 
-// (wg_splitk_plan, how many K-splits to use: host arithmetic only, in gemm16_plan.hip with the rest of the 16-bit planner that calls it)
+// (wg_splitk_plan, how many K-splits to use: host arithmetic only, in gemm_plan_common.hpp with what else the two planners share)
 
 int wg_splitk_reduce(wg_ctx *ctx, const float *part, uint32_t nsplit, uint32_t M, uint32_t N, uint32_t nmats, wg_dtype dtype, void *out,
                      uint32_t ldc, uint64_t c_batch, float alpha, float beta) {

@@ -74,6 +74,8 @@ struct wg_ctx {
     std::vector<AsyncError> async_errors;
     std::string path_log; // wg_path: tags of the terminal launches since the last wg_debug_take_path (tests read which leaf a call took)
 };
+// the compute units a launch on the context's stream may use (a context created on a caller's stream does not know: the whole chip)
+static inline int wg_ctx_cus(const wg_ctx *ctx) { return ctx->compute_units > 0 ? ctx->compute_units : 256; }
 // A destroy call that arrives while THIS THREAD records a command buffer (hipStreamBeginCapture, thread-local mode) must not run now: hipFree /
 // hipStreamSynchronize from the capturing thread are prohibited and invalidate the capture. It happens -- a garbage-collected host object
 // (Python's cyclic GC, a Rust drop at scope end) owns a buffer or a command buffer -- and it is legal in the reference (wgpu keeps a dropped
@@ -199,13 +201,12 @@ int wgk_gemv_small_reduce(wg_ctx *ctx, int op, uint32_t rows_out, uint32_t k, fl
 int wgk_gemm_f32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
                  float *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha = 1.f, float beta = 0.f);
 // gemm_f32_mid.hip: bm x bn tiles (128 x 128, 128 x 64, 64 x 128 on 2 x 2 waves; 64 x 64, 64 x 32, 32 x 64 with K split over the waves), whole K per workgroup
-// for nsplit = 1; nsplit >= 2 cuts K across workgroups too (f32 slabs in the context's workspace + a reduce launch: few tiles, long K);
-// _ok: the shapes / strides it takes
-bool wgk_gemm_f32_mid_ok(uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wgk_mat m1, wgk_mat m2);
-int wgk_gemm_f32_mid(wg_ctx *ctx, bool trans, int bm, int bn, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
-                     wgk_mat m1, wgk_mat m2, float alpha, float beta, uint32_t nsplit = 1);
-int wgk_gemm_f32_skinny(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
-                        wgk_mat m1, wgk_mat m2, float alpha, float beta, uint32_t out_row_stride = 1, bool m2_kmajor = false, uint32_t ns_force = 0);
+// for nsplit = 1; nsplit >= 2 cuts K across workgroups too (f32 slabs in the context's workspace + a reduce launch: few tiles, long K).
+// Both launch only: tile, panels and K cut are the plan's (gemm32_plan.hip: gemm32_plan; gemm32_skinny_plan for the Gemv launcher's hand-off); they log its tag.
+int wgk_gemm_f32_mid(wg_ctx *ctx, const wg_gemm32_plan &p, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
+                     wgk_mat m1, wgk_mat m2, float alpha, float beta);
+int wgk_gemm_f32_skinny(wg_ctx *ctx, const wg_gemm32_plan &p, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
+                        wgk_mat m1, wgk_mat m2, float alpha, float beta, uint32_t out_row_stride = 1, bool m2_kmajor = false);
 // f16 GemmTr with N <= 16 on the few-column streaming kernel (gemm_f32_skinny.hip, T = _Float16): HBM-bound, m1 read once
 // (launch only: the K cut -- ns splits of kps, f32 slabs in `part` -- is the caller's plan, gemm16_plan.hip, and so is the slabs' reduce)
 int wgk_gemm_f16_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, __half *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
@@ -255,8 +256,7 @@ int wg_gemm_f16_panels(wg_ctx *ctx, bool tr, void *out_panel0, uint32_t ldc, con
 // byte with the read one; base_*: element 0 of each view's buffer.
 int wg_check_alias(const char *op, wg_dtype dtype, const char *wname, wg_view_shape w, const void *base_w, const char *rname, wg_view_shape r, const void *base_r);
 
-// split-K (the plan: gemm16_plan.hip; the reduce kernels: splitk.hip)
-uint32_t wg_splitk_plan(uint64_t tiles, uint32_t slots, uint32_t k_units, uint32_t min_units, uint64_t out_elems, uint64_t max_ws_bytes);
+// split-K (the plan: wg_splitk_plan, gemm_plan_common.hpp; the reduce kernels: splitk.hip)
 // f32, beta = 0: out[z][r * row_stride + c * col_stride] = alpha * sum over splits (the transposed output of few-row products)
 int wg_splitk_reduce_strided(wg_ctx *ctx, const float *part, uint32_t nsplit, uint32_t M, uint32_t N, uint32_t nmats, float *out,
                              uint32_t row_stride, uint32_t col_stride, uint64_t c_batch, float alpha);
