@@ -6,7 +6,7 @@ Everything in the table is the launcher as it was BEFORE it was split into gemm3
 the launcher's decision reads) and the log wg_debug_take_path returns after it -- from one of two sources (`src`):
   0  run on an MI355X with that commit's library: the whole chip and the masked contexts GPU_CONTEXTS;
   1  that commit's wgk_gemm_f32 (with its two launchers) compiled for the host and called with the query: the masked contexts HOST_CONTEXTS, and leading dimensions
-     no test's operands reach (the branches behind dma_ok == false). The CU count and the leading dimensions are only numbers in the launcher's host arithmetic, so
+     no operand of the tests of that commit reached (the branches behind dma_ok == false; tests/test_gpu_far_views.py runs them on a device since). The CU count and the leading dimensions are only numbers in the launcher's host arithmetic, so
      no device is needed; the program (`--harness`: launches and workspace requests are no-ops, wg_path records, the slab reduces and transposes log their tags) is
      a scratch build and not part of the repository. It reads one query per line (the first 18 FIELDS) and prints "status<TAB>log". The script first runs every src-0
      row through it as well and stops unless it gives the recorded log for all of them.
@@ -54,6 +54,7 @@ RETURNS = ("empty product: nothing to do (api.hip returns before the launcher; t
            "refused by wgk_gemm_f32_skinny (matrices x panels > 65535)",
            "refused by wgk_gemm_f32_mid (matrices x splits > 65535)",
            "few-row form on transposed copies, M <= 64: leading dimensions past the few-column kernel's 32-bit offsets (dma_ok == false)")
+# (the last one: on a device in tests/test_gpu_far_views.py; the text above is part of the recorded table and stays as it was recorded)
 (R_EMPTY, R_MATS, R_EARLY_MID, R_FEWROW, R_SKINNYT, R_SKINNY, R_SHORTK, R_PANELS, R_MID, R_TAIL, R_SPLITK, R_BIG, R_SKINNY_ERR, R_MID_ERR, R_FEWROW_DMA) = range(len(RETURNS))
 # returns no row can take, and why (tests/test_gemm32_plan_host.py covers them through the planner's invariants)
 UNREACHED = {"Gemm: too many tiles": "more than 2^31 tiles of 256 x 128: an output of 2^46 floats",

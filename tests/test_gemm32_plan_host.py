@@ -261,7 +261,8 @@ def test_invariants_with_forced_knobs_and_odd_layouts():
 
 def test_invariants_past_the_dma_offset_limits():
     """Leading dimensions whose tiles no longer fit 32-bit byte offsets: the families that build such offsets are not taken, the few-row form falls back to
-    transposed copies (the branches behind dma_ok == false, which no real operand of a test reaches), and every rule above still holds."""
+    transposed copies (the branches behind dma_ok == false; the kernels those plans name run on real operands with such leading dimensions in
+    tests/test_gpu_far_views.py, whose thresholds tests/test_far_views_host.py finds), and every rule above still holds."""
     seen = set()
     for (M, N, K), lda, ldb, tr, beta in itertools.product(((16, 4096, 256), (64, 16384, 1024), (96, 8192, 256), (4096, 16, 1024), (512, 512, 512), (4096, 4096, 256)),
                                                           (None,) + BIG_LDS, (None,) + BIG_LDS, (False, True), (0.0, 1.0)):

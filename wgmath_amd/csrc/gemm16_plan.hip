@@ -163,6 +163,8 @@ wg_gemm16_plan gemm16_plan(const wg_gemm16_query &q) {
     const uint32_t krem = K % 64u;
     const bool k_big = K % 8u == 0 && K - krem >= 192u, k_small = K % 8u == 0 && K - krem >= 64u;
     const bool a_step_fits = trans || (uint64_t)m1.ld * 64u < (1ull << 32); // NN: a half-stage of A (32 k rows) apart in 32 bits (the DMA cursors' increments are SGPRs)
+    // (never the deciding term: off_ok asks the same product of Gemm to stay below 2^31, so a_step_fits is true wherever off_ok is -- tests/test_far_views_host.py
+    // test_a_step_fits_never_decides. Kept: it states what the kernel needs, and holds if off_ok's row count ever changes.)
     // (Leading dimensions, base addresses and batch strides: anything element-aligned since round 6. The operands come in by LDS-DMA and the results leave in 16-byte
     // stores, and both take any element-aligned address on this target -- tools/cpp/unaligned_probe.hip, unaligned_dma_probe.hip: the aligned rate at 4-byte offsets, 0.9 of
     // it at 2-byte ones. Until then such views went through padded copies: 2048^3 with one odd leading dimension 35 us instead of 25, a C at an odd offset twice the time.)
