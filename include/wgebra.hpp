@@ -413,6 +413,22 @@ struct Gemm {
     void dispatch_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<T> out, GpuTensorView<T> m1, GpuTensorView<T> m2) const {
         dispatch_generic(d, s, p, out, m1, m2, GemmVariant::GemmTr);
     }
+    // extension (wg_gemm_out32): 16-bit operands W (_Float16 / bf16; float forwards to wg_gemm_ex) with an f32 result out = alpha * op(m1) * m2 + beta * out -- the
+    // f32 accumulator of the 16-bit Gemm stored as it is. `out` is a view of float by its type. Column-major views (the row-major surface has no f32-output form).
+    template <typename W>
+    void dispatch_out32_generic(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<float> out, GpuTensorView<W> m1, GpuTensorView<W> m2,
+                                GemmVariant variant, float alpha = 1.f, float beta = 0.f) const {
+        check(wg_gemm_out32(pass.ctx(), (wg_gemm_variant)variant, dtype_of<W>::value, alpha, beta, out.buffer(), out.shape(), m1.buffer(), m1.shape(), m2.buffer(),
+                            m2.shape()));
+    }
+    template <typename W>
+    void dispatch_out32(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<W> m1, GpuTensorView<W> m2) const {
+        dispatch_out32_generic(d, s, p, out, m1, m2, GemmVariant::Gemm);
+    }
+    template <typename W>
+    void dispatch_out32_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<W> m1, GpuTensorView<W> m2) const {
+        dispatch_out32_generic(d, s, p, out, m1, m2, GemmVariant::GemmTr);
+    }
 };
 
 // gemv.rs:9-137

@@ -53,7 +53,7 @@ extern "C" {
 #define WGEBRA_HIP_ABI_VERSION 5 /* 5: wg_debug_take_path; and the round-6 additions that came without a bump: wg_copy_view, wg_timestamps_reserve,
                                     wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE, wg_debug_gemm16_plan and wg_debug_gemm32_plan (added diagnostic symbols with their two structs each); WG_ERR_ALIASED = 9 (an appended status: calls that
                                     return it used to launch kernels that raced on their own operands) with wg_debug_views_overlap; and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
-                                    that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump); wg_gemv_mixed (an added symbol);
+                                    that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump); wg_gemv_mixed (an added symbol); wg_gemm_out32 with wg_debug_gemm_out32_query (added symbols);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
 
@@ -311,6 +311,9 @@ typedef struct wg_gemm16_plan {
  * slab reduce of a K cut included; for a padded call the pad tag followed by the inner call's tags. inner (may be NULL): the query of that inner call
  * (pad plans only; else a copy of `query`). Calibrated shares are planned from flat rates (the forced pattern, WG_TUNE_F16_BALANCE = 1, ignores them). */
 int wg_debug_gemm16_plan(const wg_gemm16_query *query, const char *prefix, wg_gemm16_plan *plan, char *tags, size_t cap, wg_gemm16_query *inner);
+/* The override wg_gemm_out32's launcher applies to the query it has filled, in place, before it asks the same planner: the continuous walk off (cont = 0) and
+ * the panel form off (panels = 0, widths cleared). Nothing else changes; wg_debug_gemm16_plan on the result, with prefix "f16o32" / "bf16o32", is that call's plan. */
+int wg_debug_gemm_out32_query(wg_gemm16_query *query);
 /* The same for the f32 Gemm launcher (gemm32_plan.hip): "fill a wg_gemm32_query, ask the planner, do what the wg_gemm32_plan says". The f32 launcher reads no
  * addresses: shapes, leading dimensions, matrix strides, the CU count and the four WG_TUNE_F32_* knobs decide everything. */
 typedef struct wg_gemm32_query {
@@ -464,6 +467,40 @@ int wg_gemv_mixed(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype m_dtype,
                   wg_buf *out, wg_view_shape out_shape,
                   const wg_buf *m, wg_view_shape m_shape,
                   const wg_buf *v, wg_view_shape v_shape);
+
+/*
+ * Extension: Gemm on 16-bit operands with an f32 result -- out = alpha * op(m1) * m2 + beta * out with the f32 accumulators of the matrix cores stored as they
+ * are (a result past the f16 range, a K-chunked or residual accumulation through beta that is not re-rounded at every step, the prefill counterpart of
+ * wg_gemv_mixed). `m1` and `m2` hold in_dtype elements (WG_F16 or WG_BF16); `out` holds f32; every view shape counts elements of its own operand's type, and the
+ * bounds checks use each operand's own element size (an `out` buffer sized for 2-byte elements is refused as exceeding its buffer). in_dtype == WG_F32 forwards
+ * to wg_gemm_ex(.., WG_F32, ..) unchanged (a caller generic over the operand type needs no branch). Everything else is wg_gemm_ex's contract, with its status
+ * codes and messages: the dimension check, unknown variant, zero-sized buffers / views skipped with WG_OK, views that exceed their buffer; WG_ERR_WORKSPACE inside
+ * a recording when a padding or staging scratch would have to grow.
+ * Arithmetic:
+ *   - operands are widened exactly; the f32 accumulator is that of the 16-bit wg_gemm_ex on the same leaf -- the same MFMA chain in the same order;
+ *   - r = alpha * acc is rounded to f32 (skipped for alpha == 1), then r = fmaf(beta, c, r) with c read as the f32 it is; beta == 0 never reads `out` (NaN / Inf
+ *     there are overwritten); r is stored as it is -- there is no 16-bit rounding anywhere;
+ *   - deterministic: no atomics, K cuts are added in ascending order;
+ *   - same leaf, same accumulator: while this call and the 16-bit call for the same shape, views, knobs and context log the same leaf, one round-to-nearest-even
+ *     of this call's result to the 16-bit type IS the 16-bit call's result, bit for bit, for beta == 0 and, when the old `out` is representable in 16 bits,
+ *     for beta != 0 (every leaf rounds to f32 first).
+ * Which kernels: the plan is the 16-bit planner's for the same query (shape, leading dimensions, matrix strides and base addresses as they are, each in its own
+ * operand's elements) with the continuous tile walk and the panel form off (wg_debug_gemm_out32_query). Every other leaf is taken: the few-column kernel, 128 x 128
+ * with and without a K cut, 256 x 128, the 256 x 256 per-tile kernel (static map, tile queues, calibrated shares, split-K, cut-up tail), the padded call, the
+ * generic kernel; the WG_TUNE_F16_* knobs apply as they do to bf16. Every leaf stores f32 directly at any 4-byte-aligned address: an `out` view at an odd offset,
+ * with an odd leading dimension and an odd gap between matrices runs where it lies. The few-column leaf stores directly too (its one-split form writes the four
+ * floats of a lane; with a K cut it writes the usual f32 slabs and the f32 slab reduce finishes). The call never takes the Gemv kernels: the "1 .. 7 columns run as
+ * a Gemv" shortcut of wg_gemm_ex has no 16-bit x 16-bit -> f32 kernel to go to, and the 16-bit tile kernels take any N as it is. M or K not a multiple of 4:
+ * staged like wg_gemm_ex, the output's copy in f32.
+ *   ALIASED       : `out` shares a byte with `m1` or with `m2` -- on addresses, in 2-byte units as wg_gemv_mixed does, so `out` and `m1` may live in one buffer:
+ *                   touching is legal, one shared byte is refused. `m1` and `m2` may overlap each other.
+ * Not included: the row-major surface (wg_gemm_rm), the sharded / panel calls (wg_gemm_sharded*), the continuous walk.
+ * wg_debug_take_path: the element prefix is "f16o32." / "bf16o32."; the dtype-free tags ("splitk.reduce/ns=", "stage..>") are unchanged.
+ */
+int wg_gemm_out32(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype in_dtype, float alpha, float beta,
+                  wg_buf *out, wg_view_shape out_shape,
+                  const wg_buf *m1, wg_view_shape m1_shape,
+                  const wg_buf *m2, wg_view_shape m2_shape);
 
 /*
  * ROW_MAJOR operator surface. Replaces composing the reference's shaders with

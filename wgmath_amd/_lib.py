@@ -159,6 +159,8 @@ def _load() -> ctypes.CDLL:
         "wg_gemm_ex": (ci, [vp, ci, ci, ctypes.c_float, ctypes.c_float, vp, S, vp, S, vp, S]),
         "wg_gemv": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),
         "wg_gemv_mixed": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),
+        "wg_gemm_out32": (ci, [vp, ci, ci, ctypes.c_float, ctypes.c_float, vp, S, vp, S, vp, S]),
+        "wg_debug_gemm_out32_query": (ci, [ctypes.POINTER(Gemm16QueryC)]),
         "wg_gemm_rm": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),
         "wg_gemv_rm": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),
         "wg_gemv_reduce": (ci, [vp, ci, ci, ci, vp, vp, S, vp, S]),

@@ -83,16 +83,21 @@ inline uint32_t up8(uint32_t x) { return (x + 7u) & ~7u; }
 // zero-padded copy (the length rounded up to 8; zeros add nothing to a dot product), the usual kernels run, and a padded result is copied back
 // into the output view -- HBM-bound passes in a fourth context scratch (it cannot grow inside a recording).
 // the Gemm launcher of an element type (f32; the 16-bit family compiled for f16 and for bf16)
-int gemm_launch(wg_ctx *ctx, bool tr, wg_dtype dtype, uint32_t M, uint32_t N, uint32_t K, uint32_t mats, void *C, uint32_t ldc, uint64_t c_batch, wgk_mat A, wgk_mat B,
-                float alpha, float beta) {
+// (odt: the element type of C -- dtype itself, or WG_F32 over 16-bit operands: wg_gemm_out32)
+int gemm_launch(wg_ctx *ctx, bool tr, wg_dtype dtype, wg_dtype odt, uint32_t M, uint32_t N, uint32_t K, uint32_t mats, void *C, uint32_t ldc, uint64_t c_batch, wgk_mat A,
+                wgk_mat B, float alpha, float beta) {
+    if (odt != dtype) {
+        if (dtype == WG_BF16) return wgk_gemm_bf16o32(ctx, tr, M, N, K, mats, (float *)C, ldc, c_batch, A, B, alpha, beta);
+        return wgk_gemm_f16o32(ctx, tr, M, N, K, mats, (float *)C, ldc, c_batch, A, B, alpha, beta);
+    }
     if (dtype == WG_F32) return wgk_gemm_f32(ctx, tr, M, N, K, mats, (float *)C, ldc, c_batch, A, B, alpha, beta);
     if (dtype == WG_BF16) return wgk_gemm_bf16(ctx, tr, M, N, K, mats, (wg_bf16 *)C, ldc, c_batch, A, B, alpha, beta);
     return wgk_gemm_f16(ctx, tr, M, N, K, mats, (__half *)C, ldc, c_batch, A, B, alpha, beta);
 }
 
-int gemm_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, float alpha, float beta, wg_buf *out, const View &o, const wg_buf *m1, const View &a, const wg_buf *m2,
+int gemm_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, wg_dtype odt, float alpha, float beta, wg_buf *out, const View &o, const wg_buf *m1, const View &a, const wg_buf *m2,
                 const View &b, uint32_t M, uint32_t N, uint32_t K) {
-    const size_t es = wg_dtype_size(dtype);
+    const size_t es = wg_dtype_size(dtype), ces = wg_dtype_size(odt); // (one element size per operand: the output's may differ, wg_gemm_out32)
     // Only the operands that need it are copied (round 6: a 16384 x 16384 matrix times ONE column -- N % 4 != 0, nothing else -- paid 800 us for the copy
     // of the matrix, 177 us now): a dimension that is not a multiple of 4 is rounded up to 8 in the two operands that carry it, an operand
     // whose own view is not vec4-aligned is copied at the (possibly padded) sizes, the others are used where they lie.
@@ -103,12 +108,13 @@ int gemm_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, float alpha, float beta, w
     if (ae * mats >= (1ull << 32) || be * mats >= (1ull << 32) || ce * mats >= (1ull << 32))
         return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: operands too large for the staging path of views that are not vec4-aligned");
     void *ws = nullptr;
-    if (int rc = wg_ctx_stage_workspace(ctx, (size_t)((ae + be + ce) * mats * es), &ws)) return rc;
+    // (a padded operand has a dimension rounded up to 8, so every region is a multiple of 16 bytes and the output's copy starts 16-byte aligned)
+    if (int rc = wg_ctx_stage_workspace(ctx, (size_t)((ae + be) * mats * es + ce * mats * ces), &ws)) return rc;
     char *ap = (char *)ws, *bp = ap + ae * mats * es, *cp = bp + be * mats * es;
     wg_path(ctx, "stage%s>", !sc ? "" : beta != 0.f ? "/c=seed" : "/c");
     const uint32_t a_ld = tr ? Kp : Mp;
     wgk_mat A = { elem_ptr(m1, a.offset, dtype), a.stride, a.stride_mat }, B = { elem_ptr(m2, b.offset, dtype), b.stride, b.stride_mat };
-    void *C = (void *)elem_ptr(out, o.offset, dtype);
+    void *C = (void *)elem_ptr(out, o.offset, odt);
     uint32_t ldc = o.stride;
     uint64_t c_batch = o.stride_mat;
     if (sa) {
@@ -121,12 +127,12 @@ int gemm_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, float alpha, float beta, w
     }
     if (sc) {
         if (beta != 0.f)
-            if (int rc = wgk_stage_copy(ctx, dtype, cp, Mp, ce, Mp, Np, C, o.stride, o.stride_mat, M, N, mats)) return rc;
+            if (int rc = wgk_stage_copy(ctx, odt, cp, Mp, ce, Mp, Np, C, o.stride, o.stride_mat, M, N, mats)) return rc;
         C = cp; ldc = Mp; c_batch = ce;
     }
-    if (int rc = gemm_launch(ctx, tr, dtype, Mp, Np, Kp, mats, C, ldc, c_batch, A, B, alpha, beta)) return rc;
+    if (int rc = gemm_launch(ctx, tr, dtype, odt, Mp, Np, Kp, mats, C, ldc, c_batch, A, B, alpha, beta)) return rc;
     if (!sc) return WG_OK;
-    return wgk_stage_copy(ctx, dtype, (void *)elem_ptr(out, o.offset, dtype), o.stride, o.stride_mat, M, N, cp, Mp, ce, Mp, Np, mats);
+    return wgk_stage_copy(ctx, odt, (void *)elem_ptr(out, o.offset, odt), o.stride, o.stride_mat, M, N, cp, Mp, ce, Mp, Np, mats);
 }
 
 int gemv_staged(wg_ctx *ctx, bool tr, wg_dtype dtype, wg_buf *out, const View &o, const wg_buf *m, const View &mm, const wg_buf *v, const View &vv,
@@ -276,11 +282,46 @@ int wg_gemm_ex(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype dtype, float alpha
     //  tests/test_gpu_parity.py::test_gemm_f32_any_number_of_columns fails on them without the copies)
     const bool n_free = dtype != WG_F32 || m_rows > 128u; // (f32 with up to 128 rows: the few-row forms compute the transposed product, where N is the length that must be a multiple of 4)
     if ((o.cols % 4 && !n_free) || m_cols % 4 || m_rows % 4)
-        return gemm_staged(ctx, tr, dtype, alpha, beta, out, o, m1, a, m2, b, m_rows, o.cols, m_cols);
+        return gemm_staged(ctx, tr, dtype, dtype, alpha, beta, out, o, m1, a, m2, b, m_rows, o.cols, m_cols);
     wgk_mat A = { elem_ptr(m1, a.offset, dtype), a.stride, a.stride_mat };
     wgk_mat B = { elem_ptr(m2, b.offset, dtype), b.stride, b.stride_mat };
     void *C = (void *)elem_ptr(out, o.offset, dtype);
-    return gemm_launch(ctx, tr, dtype, m_rows, o.cols, m_cols, o.mats, C, o.stride, o.stride_mat, A, B, alpha, beta);
+    return gemm_launch(ctx, tr, dtype, dtype, m_rows, o.cols, m_cols, o.mats, C, o.stride, o.stride_mat, A, B, alpha, beta);
+}
+
+// wg_gemm_ex with an f32 `out` over 16-bit operands. The same checks in the same order with the same messages; bounds per operand's own element size; the aliasing
+// rule on addresses (out against either 16-bit operand in 2-byte units). Never the Gemv kernels: the 16-bit tile kernels take any N as it is.
+int wg_gemm_out32(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype in_dtype, float alpha, float beta, wg_buf *out, wg_view_shape out_shape,
+                  const wg_buf *m1, wg_view_shape m1_shape, const wg_buf *m2, wg_view_shape m2_shape) {
+    const wg_buf *bufs[3] = { out, m1, m2 };
+    if (int rc = check_common("Gemm", ctx, in_dtype, bufs, 3)) return rc;
+    if (in_dtype == WG_F32) return wg_gemm_ex(ctx, variant, WG_F32, alpha, beta, out, out_shape, m1, m1_shape, m2, m2_shape); // (a caller generic over the operand type needs no branch)
+    if ((int)variant < 0 || (int)variant > 3) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: unknown variant %d", (int)variant);
+    const bool tr = variant == WG_GEMM_TR || variant == WG_GEMM_TR_FAST;
+    const View o = mk(out_shape), a = mk(m1_shape), b = mk(m2_shape);
+
+    const uint32_t m_rows = tr ? a.cols : a.rows, m_cols = tr ? a.rows : a.cols;
+    if (m_cols != b.rows || m_rows != o.rows || o.cols != b.cols || o.mats != a.mats || o.mats != b.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH,
+                            "Gemm: dimension mismatch. (out [%u,%u,%u], m1 [%u,%u,%u]%s, m2 [%u,%u,%u])", o.rows, o.cols, o.mats,
+                            a.rows, a.cols, a.mats, tr ? "^T" : "", b.rows, b.cols, b.mats);
+    if (out->bytes == 0 || m1->bytes == 0 || m2->bytes == 0) return WG_OK;
+    if (o.rows == 0 || o.mats == 0) return WG_OK;
+    if (o.cols == 0) return WG_OK;
+
+    if (int rc = check_bounds("Gemm", "out", o, out, WG_F32)) return rc;
+    if (int rc = check_bounds("Gemm", "m1", a, m1, in_dtype)) return rc;
+    if (int rc = check_bounds("Gemm", "m2", b, m2, in_dtype)) return rc;
+    if (int rc = check_alias_f32_u16("Gemm", "out", o, out->ptr, "m1", a, m1->ptr)) return rc;
+    if (int rc = check_alias_f32_u16("Gemm", "out", o, out->ptr, "m2", b, m2->ptr)) return rc;
+
+    WG_HIP_TRY(hipSetDevice(ctx->device));
+    // lengths the kernels do not take as they are (M and K; any N runs as it is on the 16-bit kernels): zero-padded copies, the output's in f32
+    if (m_cols % 4 || m_rows % 4) return gemm_staged(ctx, tr, in_dtype, WG_F32, alpha, beta, out, o, m1, a, m2, b, m_rows, o.cols, m_cols);
+    wgk_mat A = { elem_ptr(m1, a.offset, in_dtype), a.stride, a.stride_mat };
+    wgk_mat B = { elem_ptr(m2, b.offset, in_dtype), b.stride, b.stride_mat };
+    void *C = (void *)elem_ptr(out, o.offset, WG_F32);
+    return gemm_launch(ctx, tr, in_dtype, WG_F32, m_rows, o.cols, m_cols, o.mats, C, o.stride, o.stride_mat, A, B, alpha, beta);
 }
 
 int wg_gemv(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype, wg_buf *out, wg_view_shape out_shape, const wg_buf *m,

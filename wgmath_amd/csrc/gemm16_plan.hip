@@ -97,6 +97,23 @@ uint32_t bal_plan(const double rel[8], uint32_t tiles, uint32_t S, bool forced, 
     return pairs;
 }
 
+// the c_stream rule (GemmArgs::c_stream) for a result of out_elem_bytes per element: 2 in every plan; the out32 launcher asks again with 4
+uint32_t gemm16_c_stream(const wg_gemm16_query &q, uint32_t out_elem_bytes) {
+#ifdef WG_FORCE_C_STREAM
+    return WG_FORCE_C_STREAM; // experiment builds
+#endif
+    const uint64_t MiB = 1ull << 20, ab = ((uint64_t)q.M * q.K + (uint64_t)q.K * q.N) * q.nmats * 2u, cb = (uint64_t)q.M * q.N * q.nmats * out_elem_bytes;
+    return (q.beta == 0.f && ab <= 256u * MiB && ab + cb > 256u * MiB) ? 1u : 0u;
+}
+
+// wg_gemm_out32's override of the query its launcher fills: the plan is the 16-bit call's with the continuous walk and the panel form off
+wg_gemm16_query gemm16_out32_query(wg_gemm16_query q) {
+    q.cont = 0;
+    q.panels = 0; q.panel_cols = q.panel_n_main = q.panel_n_tail = 0;
+    for (int t = 0; t < 8; ++t) q.panel_tail_cols[t] = 0;
+    return q;
+}
+
 namespace {
 // WG_GEMM16_UNSUPPORTED: no launch, the call returns `status` (with the message, if one is given)
 wg_gemm16_plan no_launch(wg_gemm16_plan p, int status, const char *fmt = nullptr, ...) {
@@ -127,11 +144,8 @@ wg_gemm16_plan gemm16_plan(const wg_gemm16_query &q) {
     if (M == 0 || N == 0 || nmats == 0) return no_launch(p, panels ? WG_ERR_UNSUPPORTED : WG_OK);
     if (nmats > 65535) return no_launch(p, WG_ERR_UNSUPPORTED, "Gemm: more than 65535 matrices in one call");
     {   // the result past the caches when it would push the operands out of the Infinity Cache (see GemmArgs::c_stream); beta != 0 reads C back
-        const uint64_t MiB = 1ull << 20, ab = ((uint64_t)M * K + (uint64_t)K * N) * nmats * 2u, cb = (uint64_t)M * N * nmats * 2u;
-        p.c_stream = (beta == 0.f && ab <= 256u * MiB && ab + cb > 256u * MiB) ? 1u : 0u;
-#ifdef WG_FORCE_C_STREAM
-        p.c_stream = WG_FORCE_C_STREAM; // experiment builds
-#endif
+        const uint64_t MiB = 1ull << 20;
+        p.c_stream = gemm16_c_stream(q, 2u);
         // (read by gemm_f16_t128.hip only: one column of 128-wide tiles. Gemm only: GemmTr's k-contiguous A arrives as 64-byte row pieces, two per line at different times)
         p.a_nt = (!trans && N <= 128u && (uint64_t)M * K * 2u >= 384u * MiB) ? 1u : 0u;
     }
@@ -478,6 +492,13 @@ extern "C" int wg_debug_gemm16_plan(const wg_gemm16_query *query, const char *pr
         q = gemm16_pad_inner(q, p);
     }
     if (cap) snprintf(tags, cap, "%s", log.c_str());
+    return WG_OK;
+}
+
+// The override wg_gemm_out32's launcher applies to its query before it asks the planner (tests/test_gemm_out32_host.py; no context, no device).
+extern "C" int wg_debug_gemm_out32_query(wg_gemm16_query *query) {
+    if (!query) return wg_set_error(WG_ERR_INVALID_ARG, "wg_debug_gemm_out32_query: NULL argument");
+    *query = gemm16_out32_query(*query);
     return WG_OK;
 }
 

@@ -8,6 +8,10 @@
 wg_gemm16_plan gemm16_plan(const wg_gemm16_query &q);
 // the query of the call a WG_GEMM16_PAD plan makes on its padded copies (the copied operands: dense, 16-byte aligned, matrix strides rounded up to 8 elements)
 wg_gemm16_query gemm16_pad_inner(const wg_gemm16_query &q, const wg_gemm16_plan &p);
+// wg_gemm_out32 (16-bit operands, f32 result): the same planner on the same query with the continuous walk and the panel form off -- the override its launcher
+// applies -- and the c_stream rule for an output of out_elem_bytes per element (the plan's own c_stream counts 2)
+wg_gemm16_query gemm16_out32_query(wg_gemm16_query q);
+uint32_t gemm16_c_stream(const wg_gemm16_query &q, uint32_t out_elem_bytes);
 
 // The launch-log tags (wg_path) of a plan's own launches, in launch order, with the element prefix "f16" or "bf16": the launcher logs exactly these.
 // WG_GEMM16_M16: [0] the whole tiles (`bal_on`: calibrated shares found something to move), [1] and [2] the cut-up tail and its reduce.

@@ -204,8 +204,8 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
     }
     const wg16_elem_t *A = g.a + z * g.a_batch + (TRANS_A ? (uint64_t)k_begin : (uint64_t)k_begin * g.lda);
     const wg16_elem_t *B = g.b + z * g.b_batch + k_begin;
-    wg16_elem_t *C = g.c + z * g.c_batch;
-    const bool paneled = g.panel.cols != 0; // workgroup-uniform
+    wg16_out_t *C = g.c + z * g.c_batch;
+    const bool paneled = !kOut32 && g.panel.cols != 0; // workgroup-uniform (the out32 builds have no paneled form)
     if (paneled) { // the epilogue indexes columns globally: C + col * ldc; panel p's columns start at its own base: the cube's columns are col_stride
         // apart, this rank's slot of panel p starts slot_rows * np(p) elements into it (C already points slot_rows * cols into panel 0)
         // (64-bit products run on the vector unit even when uniform: back to scalar registers by hand, C is pinned in SGPRs below)
@@ -779,7 +779,8 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
 #define WG_EPI_STORE -1 // -1: by GemmArgs::c_stream (shipped); experiments: 0 plain, 1 nt, 2 sc1, 3 sc0 sc1, 4 sc1 nt for every launch
 #endif
     // (u, p) in the lane's own layout: rows row0 + 32 p .. + 7 of column n0 + 128 wn + 16 u + i16, alpha / beta applied, rounded once
-    auto pack = [&](int u, int p, bool ok, const wg16_elem_t *cc) -> half8_t {
+    // (wg_gemm_out32: the same r, kept as 8 floats -- c is read as the f32 it is, 32 bytes at an address that is only 4-byte aligned, and nothing is narrowed)
+    auto pack = [&](int u, int p, bool ok, const wg16_out_t *cc) -> out8_t {
         float r[8];
 #pragma unroll
         for (int q = 0; q < 4; ++q) { // (odd lane rows of the swap-free Gemm: the pair's tiles in exchanged order)
@@ -791,18 +792,29 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
             for (int q = 0; q < 8; ++q) r[q] *= alpha;
         }
         if (beta != 0.f && ok) { // beta == 0 never reads C
-            const half8_t c = *reinterpret_cast<const half8_u *>(cc + 32 * p);
+            const out8_t c = *reinterpret_cast<const out8_u *>(cc + 32 * p);
 #pragma unroll
             for (int q = 0; q < 8; ++q) r[q] = fmaf(beta, (float)c[q], r[q]);
         }
-        half8_t v;
+        out8_t v;
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = (wg16_elem_t)r[q];
+        for (int q = 0; q < 8; ++q) v[q] = (wg16_out_t)r[q];
         return v;
     };
     // (every hand-written store carries its own `s_nop 1`: a store of more than 64 bits reads its data registers AFTER it issues, the compiler's hazard
     // recognizer does not look inside an asm statement, and a read-out of the next pack into the same registers right behind the store changed the first
     // dword for lanes 12 .. 15 of every row -- seen in the continuous kernel, round 5)
+#ifdef WG_GEMM16_OUT32
+    // the lane's 8 consecutive rows are two 16-byte stores (rows + 0..3, + 4..7) in the flavour c_stream picks, each hand-written one with its own s_nop
+    auto store8 = [&](float *dst, out8_t v) {
+        if (WG_ABLATE & 32) return;
+        const floatx4 lo = { v[0], v[1], v[2], v[3] }, hi = { v[4], v[5], v[6], v[7] };
+        if (c_stream) {
+            asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(dst), "v"(lo) : "memory");
+            asm volatile("global_store_dwordx4 %0, %1, off offset:16 sc1 nt\n\ts_nop 1" ::"v"(dst), "v"(hi) : "memory");
+        } else *reinterpret_cast<out8_u *>(dst) = v;
+    };
+#else
     auto store8 = [&](wg16_elem_t *dst, half8_t v) {
         if (paneled) { // write-through to memory: when the store is acknowledged a copy engine may read it
             if constexpr (WG_PANEL_STORE == 0) *reinterpret_cast<half8_u *>(dst) = v; // (timing experiments only: NOT visible to a copy engine in time)
@@ -819,15 +831,50 @@ __device__ __forceinline__ void m16_tile(const GemmArgs &g, const uint32_t bid, 
             else asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(dst), "v"(v) : "memory");
         }
     };
+#endif
     // (A store instruction covers 16 columns x 64 bytes -- half lines -- and an idle CU gets a tile out four times faster when 16 consecutive lanes
     // cover 256 contiguous bytes (tools/cpp/store_probe.hip). Both ways to that layout were built and measured in the kernel -- a DPP exchange between
     // the halves of the 16-lane rows, and a round trip of the rounded tile through the idle LDS -- and neither paid: the stores of a tile boundary
     // are bound by what the chip takes from 256 CUs at once, not by their issue; 8192 x 8192 x 512 92.5 -> 97 us: profiles/r03_evidence.md section 9.)
+#ifdef WG_GEMM16_OUT32
+    // Whole tiles: the lanes kg = 0 .. 3 of a column hold 32 consecutive rows = 128 bytes, 32 of them each, and a store instruction takes 16 bytes per lane: stored as
+    // they lie, an instruction writes 16-byte pieces with 16-byte holes -- half sectors, which the streamed flavour (`sc1 nt`: written through, nothing combines
+    // them) pays for dearly (8192^2 x 1024: 418 us against the 16-bit kernel's 129, profiles/gemm_out32.txt). So the four lanes exchange their halves first -- one
+    // v_permlane16_swap and one v_permlane32_swap per register: lane kg ends up with rows 4 kg .. + 3 and 16 + 4 kg .. + 3 of the 32 -- and each instruction writes
+    // 64 contiguous bytes per column, the 16-bit kernel's footprint. Same values to the same addresses. Ragged tiles keep the plain form below (per-lane guards).
+    if (full_tile && !(WG_ABLATE & 32)) {
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            float *cc = C + (uint64_t)(n0 + 128u * wn + 16u * u + i16) * ldc + row0;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                const out8_t v = pack(u, p, true, cc);
+                uintx4 x = __builtin_bit_cast(uintx4, floatx4{ v[0], v[1], v[2], v[3] }), y = __builtin_bit_cast(uintx4, floatx4{ v[4], v[5], v[6], v[7] });
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    uintx2 r = __builtin_amdgcn_permlane16_swap(x[q], y[q], false, false); // odd lane rows of x <-> even lane rows of y: (lo, lo') | (hi, hi') per pair of lane rows
+                    r = __builtin_amdgcn_permlane32_swap(r[0], r[1], false, false);        // lane rows 2, 3 of x <-> lane rows 0, 1 of y
+                    x[q] = r[0]; y[q] = r[1];
+                }
+                float *d = cc + 32 * p - 4 * kg; // the 128 bytes start 8 kg rows above this lane's own; its pieces: 4 kg rows in, and 16 rows further
+                const floatx4 lo = __builtin_bit_cast(floatx4, x), hi = __builtin_bit_cast(floatx4, y);
+                if (c_stream) {
+                    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(d), "v"(lo) : "memory");
+                    asm volatile("global_store_dwordx4 %0, %1, off offset:64 sc1 nt\n\ts_nop 1" ::"v"(d), "v"(hi) : "memory");
+                } else {
+                    typedef floatx4 __attribute__((aligned(4))) floatx4_u;
+                    *reinterpret_cast<floatx4_u *>(d) = lo;
+                    *reinterpret_cast<floatx4_u *>(d + 16) = hi;
+                }
+            }
+        }
+    } else
+#endif
 #pragma unroll
     for (int u = 0; u < 8; ++u) {
         const uint32_t col = n0 + 128u * wn + 16u * u + i16;
         if (!full_tile && col >= g.N) continue;
-        wg16_elem_t *cc = C + (uint64_t)col * ldc + row0;
+        wg16_out_t *cc = C + (uint64_t)col * ldc + row0;
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
             if (!(full_tile || row0 + 32 * p < g.M)) continue; // 8 consecutive rows, all in or all out (M % 8 == 0)
@@ -909,6 +956,7 @@ __global__ __launch_bounds__(256, 1) void WG16_SYM(gemm_, _m16_kernel)(GemmArgs 
 }
 
 
+#ifndef WG_GEMM16_OUT32 // (wg_gemm_out32 never takes the continuous walk: the out32 builds leave its kernel out)
 // The continuous form's 64 accumulator quads live in a[0:255] BY NAME: left to the compiler, accumulators that are live across a tile's epilogue inside
 // an outer loop get copied to VGPRs wholesale at the inner loop's exit (on top of the fragments that must stay live there), spilled to scratch and shuffled
 // inside the multiply loop (three cuts, ISA read each time: profiles/r05_evidence.md section 3). So the multiply (a tile's first one with C = 0) and the read-out are inline
@@ -1385,6 +1433,7 @@ __global__ __launch_bounds__(256, 1) void WG16_SYM(gemm_, _m16c_kernel)(GemmArgs
     if (first >= g.sched_tiles) return;
     m16_cont<TRANS_A, STREAM, ALPHA1>(g, smem, first, (int32_t)gridDim.x, (g.sched_tiles - 1u - first) / gridDim.x + 1u);
 }
+#endif // !WG_GEMM16_OUT32
 
 // (Round 2's persistent form -- one workgroup per CU calling m16_tile per tile, a barrier in between -- measured 0.5-1 % slower than letting the hardware re-dispatch a
 // workgroup per tile, profiles/r02_evidence.md section 3c, and is gone: what a walk gains is the overlap across the tile boundary, which is m16_cont above.)
@@ -1404,15 +1453,15 @@ __global__ __launch_bounds__(256) void WG16_SYM(gemm_, _tail_reduce)(GemmArgs g)
         const float4 q = *reinterpret_cast<const float4 *>(p + (uint64_t)i * g.tail_tiles * 65536u);
         s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
     }
-    wg16_elem_t *o = g.c + (uint64_t)col * g.ldc + row;
-    struct alignas(2) h4 { wg16_elem_t v[4]; }; // (C at any element-aligned address)
+    wg16_out_t *o = g.c + (uint64_t)col * g.ldc + row;
+    typedef out4_u h4; // (C at any element-aligned address; wg_gemm_out32: four floats, stored as they are)
     if (g.alpha != 1.f) { s.x *= g.alpha; s.y *= g.alpha; s.z *= g.alpha; s.w *= g.alpha; }
     if (g.beta != 0.f) {
         const h4 t = *reinterpret_cast<const h4 *>(o);
         s.x = fmaf(g.beta, (float)t.v[0], s.x); s.y = fmaf(g.beta, (float)t.v[1], s.y);
         s.z = fmaf(g.beta, (float)t.v[2], s.z); s.w = fmaf(g.beta, (float)t.v[3], s.w);
     }
-    const h4 r = { { (wg16_elem_t)s.x, (wg16_elem_t)s.y, (wg16_elem_t)s.z, (wg16_elem_t)s.w } };
+    const h4 r = { { (wg16_out_t)s.x, (wg16_out_t)s.y, (wg16_out_t)s.z, (wg16_out_t)s.w } };
     *reinterpret_cast<h4 *>(o) = r;
 }
 
@@ -1484,6 +1533,12 @@ int pad_copy(wg_ctx *ctx, wg16_elem_t *dst, uint32_t ld_dst, uint64_t dst_batch,
     return wgk_stage_copy(ctx, WG16_DTYPE, dst, ld_dst, dst_batch, rd, cd, src, ld_src, src_batch, rs, cs, nmats);
 }
 
+// ... of the output (its own element type: f32 for wg_gemm_out32)
+int pad_copy_c(wg_ctx *ctx, wg16_out_t *dst, uint32_t ld_dst, uint64_t dst_batch, uint32_t rd, uint32_t cd, const wg16_out_t *src, uint32_t ld_src,
+               uint64_t src_batch, uint32_t rs, uint32_t cs, uint32_t nmats) {
+    return wgk_stage_copy(ctx, WG16_OUT_DTYPE, dst, ld_dst, dst_batch, rd, cd, src, ld_src, src_batch, rs, cs, nmats);
+}
+
 template <bool TRANS>
 void launch_m16(wg_ctx *ctx, dim3 grid, const GemmArgs &g) {
     hipLaunchKernelGGL((WG16_SYM(gemm_, _m16_kernel)<TRANS>), grid, dim3(256), 0, ctx->stream, g);
@@ -1492,6 +1547,7 @@ void launch_m16(wg_ctx *ctx, dim3 grid, const GemmArgs &g) {
 // The plan's whole 256 x 256 tiles (ids 0 .. ntiles - 1): the continuous walk, or one workgroup per tile on the static map, the tile queues or calibrated shares.
 int launch_tiles(wg_ctx *ctx, wg_gemm16_query q, wg_gemm16_plan p, GemmArgs gm, uint32_t ntiles) {
     const bool trans = q.trans != 0;
+#ifndef WG_GEMM16_OUT32
     if (p.cont) {
         const dim3 grid(p.nwg), block(256);
         gm.sched = nullptr; gm.sched_tiles = (uint32_t)((uint64_t)ntiles * q.nmats);
@@ -1504,6 +1560,9 @@ int launch_tiles(wg_ctx *ctx, wg_gemm16_query q, wg_gemm16_plan p, GemmArgs gm, 
         if (trans) by_stream(std::true_type{}); else by_stream(std::false_type{});
         return WG_OK;
     }
+#else
+    if (p.cont) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: the continuous walk has no f32-output form"); // (never planned: gemm16_out32_query)
+#endif
     if (p.queues) {
         if (!ctx->tile_queues) {
             if (ctx->recording) return wg_set_error(WG_ERR_WORKSPACE, "Gemm: the tile queues are needed while recording: run the call once outside the recording first");
@@ -1585,19 +1644,22 @@ int run_m16(wg_ctx *ctx, const wg_gemm16_query &q, const wg_gemm16_plan &p, Gemm
     return WG_OK;
 }
 
-int gemm16(wg_ctx *ctx, bool padded, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_ext_t *out, uint32_t out_ld, uint64_t out_batch,
+int gemm16(wg_ctx *ctx, bool padded, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_oext_t *out, uint32_t out_ld, uint64_t out_batch,
            wgk_mat m1, wgk_mat m2, float alpha, float beta, const wgk_panels *panels);
 
 // WG_GEMM16_PAD: zero-padded dense copies of what does not qualify in the context's padding scratch, the same call on those (gemm16_pad_inner: its shapes), and --
 // if the output was padded too -- the result copied back
-int run_pad(wg_ctx *ctx, const wg_gemm16_query &q, const wg_gemm16_plan &p, wg16_ext_t *out, wgk_mat m1, wgk_mat m2) {
+int run_pad(wg_ctx *ctx, const wg_gemm16_query &q, const wg_gemm16_plan &p, wg16_oext_t *out, wgk_mat m1, wgk_mat m2) {
     const wg_gemm16_query in = gemm16_pad_inner(q, p);
     const bool trans = q.trans != 0;
     const uint32_t M = q.M, N = q.N, K = q.K, nmats = q.nmats, Mp = p.Mp, Kp = p.Kp;
     const uint64_t a_sz = p.a_ok ? 0 : in.a_batch, b_sz = p.b_ok ? 0 : in.b_batch;
     void *ws = nullptr;
-    if (int rc = wg_ctx_pad_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
-    wg16_elem_t *ap = (wg16_elem_t *)ws, *bp = ap + a_sz * nmats, *cp = bp + b_sz * nmats;
+    // (the planner counts the padded output at 2 bytes per element: an f32 one takes that much again; its region starts 16-byte aligned like the others)
+    const uint64_t c_extra = kOut32 && !p.c_ok ? in.c_batch * nmats * 2u : 0u;
+    if (int rc = wg_ctx_pad_workspace(ctx, (size_t)(p.workspace_bytes + c_extra), &ws)) return rc;
+    wg16_elem_t *ap = (wg16_elem_t *)ws, *bp = ap + a_sz * nmats;
+    wg16_out_t *cp = (wg16_out_t *)(bp + b_sz * nmats);
     wg_path(ctx, "%s", gemm16_tags(p, WG16_TAG, false).tag[0]);
     wgk_mat a2 = m1, b2 = m2;
     if (!p.a_ok) { // op(A) is M x K: stored M x K or, transposed, K x M
@@ -1611,13 +1673,13 @@ int run_pad(wg_ctx *ctx, const wg_gemm16_query &q, const wg_gemm16_plan &p, wg16
     }
     if (p.c_ok) return gemm16(ctx, true, trans, in.M, N, in.K, nmats, out, in.ldc, in.c_batch, a2, b2, q.alpha, q.beta, nullptr);
     if (p.c_seed) // the padded output starts as a copy of the old one
-        if (int rc = pad_copy(ctx, cp, Mp, in.c_batch, Mp, N, (const wg16_elem_t *)out, q.ldc, q.c_batch, M, N, nmats)) return rc;
-    if (int rc = gemm16(ctx, true, trans, in.M, N, in.K, nmats, (wg16_ext_t *)cp, in.ldc, in.c_batch, a2, b2, q.alpha, q.beta, nullptr)) return rc;
-    return pad_copy(ctx, (wg16_elem_t *)out, q.ldc, q.c_batch, M, N, cp, Mp, in.c_batch, M, N, nmats);
+        if (int rc = pad_copy_c(ctx, cp, Mp, in.c_batch, Mp, N, (const wg16_out_t *)out, q.ldc, q.c_batch, M, N, nmats)) return rc;
+    if (int rc = gemm16(ctx, true, trans, in.M, N, in.K, nmats, (wg16_oext_t *)cp, in.ldc, in.c_batch, a2, b2, q.alpha, q.beta, nullptr)) return rc;
+    return pad_copy_c(ctx, (wg16_out_t *)out, q.ldc, q.c_batch, M, N, cp, Mp, in.c_batch, M, N, nmats);
 }
 
 // `padded`: the inner call of a padded call (run_pad), which must not pad again
-int gemm16(wg_ctx *ctx, bool padded, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_ext_t *out, uint32_t out_ld, uint64_t out_batch,
+int gemm16(wg_ctx *ctx, bool padded, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_oext_t *out, uint32_t out_ld, uint64_t out_batch,
            wgk_mat m1, wgk_mat m2, float alpha, float beta, const wgk_panels *panels) {
     wg_gemm16_query q = {};
     q.trans = trans; q.M = M; q.N = N; q.K = K; q.nmats = nmats;
@@ -1632,17 +1694,21 @@ int gemm16(wg_ctx *ctx, bool padded, bool trans, uint32_t M, uint32_t N, uint32_
     q.cus = (uint32_t)(ctx->compute_units > 0 ? ctx->compute_units : 256);
     q.tile = ctx->tuning[WG_TUNE_F16_TILE]; q.sched = ctx->tuning[WG_TUNE_F16_SCHED]; q.cont = ctx->tuning[WG_TUNE_F16_CONT]; q.balance = ctx->tuning[WG_TUNE_F16_BALANCE];
     q.uneven_xcds = ctx->uneven_xcds; q.recording = ctx->recording; q.bal_valid = ctx->bal.valid; q.padded = padded;
+    // wg_gemm_out32: the 16-bit planner's plan for the same query -- leading dimension, matrix stride and base address of `out` as they are (its f32 stores take any
+    // 4-byte-aligned address, so whatever the planner concludes from them is safe) -- with the continuous walk and the panel form off
+    if constexpr (kOut32) q = gemm16_out32_query(q);
     const wg_gemm16_plan p = gemm16_plan(q);
 
     GemmArgs g;
     g.a = (const wg16_elem_t *)m1.ptr; g.lda = m1.ld; g.a_batch = m1.batch;
     g.b = (const wg16_elem_t *)m2.ptr; g.ldb = m2.ld; g.b_batch = m2.batch;
-    g.c = (wg16_elem_t *)out; g.ldc = out_ld; g.c_batch = out_batch;
+    g.c = (wg16_out_t *)out; g.ldc = out_ld; g.c_batch = out_batch;
     g.M = M; g.N = N; g.K = K;
     g.alpha = alpha; g.beta = beta;
     g.tiles_m = p.tiles_m; g.tiles_n = p.tiles_n;
     g.nsplit = p.nsplit; g.k_per_split = p.k_per_split; g.part = nullptr;
     g.c_stream = p.c_stream; g.a_nt = p.a_nt;
+    if constexpr (kOut32) g.c_stream = gemm16_c_stream(q, sizeof(wg16_out_t)); // (the planner's rule counts the result at 2 bytes per element)
     g.tile_base = 0; g.tail_tiles = 0;
     g.sched = nullptr; g.sched_tiles = 0;
     g.calib = nullptr; g.bal = BalancePlan{}; g.panel = PanelArgs{};
@@ -1674,12 +1740,12 @@ int gemm16(wg_ctx *ctx, bool padded, bool trans, uint32_t M, uint32_t N, uint32_
         WG_HIP_TRY(hipGetLastError());
         break;
     }
-    if (p.nsplit > 1) return wg_splitk_reduce(ctx, g.part, p.nsplit, M, N, nmats, WG16_DTYPE, out, out_ld, out_batch, alpha, beta);
+    if (p.nsplit > 1) return wg_splitk_reduce(ctx, g.part, p.nsplit, M, N, nmats, WG16_OUT_DTYPE, out, out_ld, out_batch, alpha, beta);
     return WG_OK;
 }
 } // namespace
 
 int WG16_SYM(wgk_gemm_, )(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
-                 wg16_ext_t *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha, float beta, const wgk_panels *panels) {
-    return gemm16(ctx, false, trans, M, N, K, nmats, out, out_ld, out_batch, m1, m2, alpha, beta, panels);
+                 wg16_oext_t *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha, float beta, const wgk_panels *panels) {
+    return gemm16(ctx, false, trans, M, N, K, nmats, out, out_ld, out_batch, m1, m2, alpha, beta, kOut32 ? nullptr : panels);
 }

@@ -17,19 +17,42 @@
 #ifdef WG_GEMM16_BF16
 typedef __bf16 wg16_elem_t;
 typedef wg_bf16 wg16_ext_t;              // the 16-bit pointer type of the launchers' signatures (wg_internal.hpp)
-#define WG16_ID bf16
-#define WG16_TAG "bf16"
 #define WG16_DTYPE WG_BF16
 #define WG16_MFMA __builtin_amdgcn_mfma_f32_16x16x32_bf16
 #define WG16_MFMA_ASM "v_mfma_f32_16x16x32_bf16"
 #else
 typedef _Float16 wg16_elem_t;
 typedef __half wg16_ext_t;
-#define WG16_ID f16
-#define WG16_TAG "f16"
 #define WG16_DTYPE WG_F16
 #define WG16_MFMA __builtin_amdgcn_mfma_f32_16x16x32_f16
 #define WG16_MFMA_ASM "v_mfma_f32_16x16x32_f16"
+#endif
+// The OUTPUT element is a second switch (wg_gemm_out32: 16-bit operands, an f32 result). gemm_f16o32*.hip / gemm_bf16o32*.hip define WG_GEMM16_OUT32 and include the
+// sources that carry a leaf: the same loads, LDS images, MFMA chains and K cuts, and epilogues that store r = alpha * acc + beta * c as the f32 it is. Without the
+// switch the output element IS the operand element, so the f16 and bf16 builds are what they were. The out32 builds leave out what that call never launches: the
+// continuous walk, the panel stores (gemm_f16.hip) and the n-contiguous forms (gemm_f16_nt.hip is not compiled for them).
+#ifdef WG_GEMM16_OUT32
+typedef float wg16_out_t;                // what the epilogues store
+typedef float wg16_oext_t;               // ... in the launchers' signatures
+#define WG16_OUT_DTYPE WG_F32
+#ifdef WG_GEMM16_BF16
+#define WG16_ID bf16o32
+#define WG16_TAG "bf16o32"
+#else
+#define WG16_ID f16o32
+#define WG16_TAG "f16o32"
+#endif
+#else
+typedef wg16_elem_t wg16_out_t;
+typedef wg16_ext_t wg16_oext_t;
+#define WG16_OUT_DTYPE WG16_DTYPE
+#ifdef WG_GEMM16_BF16
+#define WG16_ID bf16
+#define WG16_TAG "bf16"
+#else
+#define WG16_ID f16
+#define WG16_TAG "f16"
+#endif
 #endif
 #define WG16_CAT3_(a, b, c) a##b##c
 #define WG16_CAT3(a, b, c) WG16_CAT3_(a, b, c)
@@ -48,6 +71,12 @@ typedef wg16_elem_t half8_t __attribute__((ext_vector_type(8)));
 // the target runs the memory pipeline in unaligned-access mode -- one global_load / global_store_dwordx4 either way, at the aligned rate for 4-byte offsets and
 // 0.9 of it for 2-byte ones (tools/cpp/unaligned_probe.hip, unaligned_dma_probe.hip; profiles/r06_unaligned_probe.txt) -- and the type says what is really known.
 typedef half8_t __attribute__((aligned(2))) half8_u;
+// 8 consecutive rows of the output, as the epilogues hold and store them: half8_t / half8_u again for a 16-bit output; 8 floats -- two 16-byte accesses at an
+// address that is only 4-byte aligned -- for wg_gemm_out32
+constexpr bool kOut32 = sizeof(wg16_out_t) == 4;
+typedef wg16_out_t out8_t __attribute__((ext_vector_type(8)));
+typedef out8_t __attribute__((aligned(sizeof(wg16_out_t)))) out8_u;
+struct alignas(sizeof(wg16_out_t)) out4_u { wg16_out_t v[4]; }; // 4 consecutive rows at any element-aligned address
 typedef short short4_t __attribute__((ext_vector_type(4)));
 typedef short short8_t __attribute__((ext_vector_type(8)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
@@ -132,7 +161,7 @@ struct PanelArgs {
 struct GemmArgs {
     const wg16_elem_t *a; uint32_t lda; uint64_t a_batch;
     const wg16_elem_t *b; uint32_t ldb; uint64_t b_batch;
-    wg16_elem_t *c; uint32_t ldc; uint64_t c_batch;
+    wg16_out_t *c; uint32_t ldc; uint64_t c_batch;
     uint32_t M, N, K;
     uint32_t tiles_m, tiles_n;
     // split-K: grid.y = nmats * nsplit, workgroup (z, s) covers K range s and writes an f32 slab of `part` ([z][s][N][M])
@@ -239,7 +268,7 @@ static __device__ __forceinline__ void tile_of(uint32_t bid, uint32_t tiles_m, u
 int generic_launch(wg_ctx *ctx, bool trans, dim3 grid, const GemmArgs &g);
 // gemm_f16_t128.hip: tm x 128 tiles, tm = 128 or 256 (g.tiles_m / g.tiles_n count those), grid = (tiles, nmats * nsplit); K per split % 64 == 0
 int t128_launch(wg_ctx *ctx, bool trans, dim3 grid, const GemmArgs &g, int tm = 128);
-// ... with m2 contiguous along N (the row-major GemmTr): Gemm only, K % 64 == 0, one split
+// ... with m2 contiguous along N (the row-major GemmTr): Gemm only, K % 64 == 0, one split (not in the out32 builds)
 int t128_launch_nt(wg_ctx *ctx, dim3 grid, const GemmArgs &g, int tm = 128);
 
 } // namespace wgf16

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(256) void WG16_SYM(gemm_, _generic_kernel)(GemmArgs
     const uint32_t z = blockIdx.z;
     const wg16_elem_t *A = g.a + z * g.a_batch;
     const wg16_elem_t *B = g.b + z * g.b_batch;
-    wg16_elem_t *C = g.c + z * g.c_batch;
+    wg16_out_t *C = g.c + z * g.c_batch;
     const uint32_t m0 = blockIdx.x * 64u, n0 = blockIdx.y * 64u;
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4; // thread owns rows 4tx..4tx+3, cols 4ty..4ty+3
     float acc[4][4] = {};
@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void WG16_SYM(gemm_, _generic_kernel)(GemmArgs
             if (m < g.M) {
                 float r = g.alpha == 1.f ? acc[p][q] : g.alpha * acc[p][q];
                 if (g.beta != 0.f) r = fmaf(g.beta, (float)C[(uint64_t)n * g.ldc + m], r);
-                C[(uint64_t)n * g.ldc + m] = (wg16_elem_t)r;
+                C[(uint64_t)n * g.ldc + m] = (wg16_out_t)r; // (wg_gemm_out32: r as it is)
             }
         }
     }

@@ -83,6 +83,7 @@ __device__ __forceinline__ void t_wait_keep_pieces(int n) { // s_waitcnt's count
 template <bool TRANS_A, int TM, bool B_NC = false>
 __global__ __launch_bounds__(256, 2) void WG16_SYM(gemm_, _t128_kernel)(GemmArgs g) {
     static_assert(!(B_NC && TRANS_A) && (!B_NC || WG_NN_NOSWAP), "n-contiguous m2: Gemm only, on the swap-free read path");
+    static_assert(!(B_NC && kOut32), "the out32 builds have no n-contiguous form");
     using Cfg = TCfg<TM>;
     constexpr int APW = Cfg::APW, PPW = Cfg::PPW, RB = Cfg::RB, T_SLOT = Cfg::SLOT, T_RING = Cfg::RING, MT = Cfg::MT, MP = Cfg::MP;
     __shared__ __attribute__((aligned(16))) char smem[T_RING * T_SLOT];
@@ -392,13 +393,13 @@ __global__ __launch_bounds__(256, 2) void WG16_SYM(gemm_, _t128_kernel)(GemmArgs
         }
         return;
     }
-    wg16_elem_t *C = g.c + z * g.c_batch;
+    wg16_out_t *C = g.c + z * g.c_batch; // (wg_gemm_out32: f32 -- the lane's 8 rows are 32 bytes at a 4-byte-aligned address, read for beta and stored as they are)
     const float alpha = g.alpha, beta = g.beta;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const uint32_t col = n0 + 64u * wn + col_in_wave(u);
         if (!full_tile && col >= g.N) continue;
-        wg16_elem_t *cc = C + (uint64_t)col * g.ldc + row0;
+        wg16_out_t *cc = C + (uint64_t)col * g.ldc + row0;
 #pragma unroll
         for (int p = 0; p < MP; ++p) {
             if (!(full_tile || row0 + 32 * p < g.M)) continue; // 8 consecutive rows, all in or all out (M % 8 == 0)
@@ -413,20 +414,21 @@ __global__ __launch_bounds__(256, 2) void WG16_SYM(gemm_, _t128_kernel)(GemmArgs
                 for (int q = 0; q < 8; ++q) r[q] *= alpha;
             }
             if (beta != 0.f) { // beta == 0 never reads C
-                const half8_t c = *reinterpret_cast<const half8_u *>(cc + 32 * p);
+                const out8_t c = *reinterpret_cast<const out8_u *>(cc + 32 * p);
 #pragma unroll
                 for (int q = 0; q < 8; ++q) r[q] = fmaf(beta, (float)c[q], r[q]);
             }
-            half8_t v;
+            out8_t v;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = (wg16_elem_t)r[q];
-            *reinterpret_cast<half8_u *>(cc + 32 * p) = v;
+            for (int q = 0; q < 8; ++q) v[q] = (wg16_out_t)r[q];
+            *reinterpret_cast<out8_u *>(cc + 32 * p) = v;
         }
     }
 }
 
 } // namespace
 
+#ifndef WG_GEMM16_OUT32
 // the B_NC instances (row-major GemmTr on mid-size outputs: gemm_f16_nt.hip's launcher). Whole K per workgroup, K % 64 == 0.
 int t128_launch_nt(wg_ctx *ctx, dim3 grid, const GemmArgs &g, int tm) {
     if (tm == 256) hipLaunchKernelGGL((WG16_SYM(gemm_, _t128_kernel)<false, 256, true>), grid, dim3(256), 0, ctx->stream, g);
@@ -434,6 +436,7 @@ int t128_launch_nt(wg_ctx *ctx, dim3 grid, const GemmArgs &g, int tm) {
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;
 }
+#endif // !WG_GEMM16_OUT32
 
 int t128_launch(wg_ctx *ctx, bool trans, dim3 grid, const GemmArgs &g, int tm) {
     if (tm == 256) {

@@ -91,7 +91,11 @@ __device__ __forceinline__ void tr_set_m0(uint32_t lds_dst) { asm volatile("s_mo
 // The 16-bit form's element type is the switch of the 16-bit Gemm family (gemm_f16_common.hpp: wg16_elem_t, WG16_MFMA, WG16_TAG, WG16_DTYPE, WG16_SYM):
 // gemm_bf16_skinny.hip defines WG_GEMM16_BF16 and includes this file, which then yields the bfloat16 instance alone, under its own kernel and launcher names.
 // (The kernel's name is the one thing the switch cannot spell: the f16 instance is an instance of gemm_f32_skinny_kernel.)
-#ifdef WG_GEMM16_BF16
+// gemm_f16o32_skinny.hip / gemm_bf16o32_skinny.hip (WG_GEMM16_OUT32: wg_gemm_out32's few-column leaf) likewise yield one 16-bit instance each whose direct store -- one
+// split -- writes the four floats of alpha * acc + beta * c as they are (wg_st_u: any 4-byte-aligned address); with a K cut the slabs and their f32 reduce are unchanged.
+#if defined(WG_GEMM16_OUT32)
+#define WG_SKINNY_KERNEL16 WG16_SYM(gemm_, _skinny_kernel)
+#elif defined(WG_GEMM16_BF16)
 #define WG_SKINNY_KERNEL16 gemm_bf16_skinny_kernel
 #else
 #define WG_SKINNY_KERNEL16 gemm_f32_skinny_kernel
@@ -359,6 +363,15 @@ __global__ __launch_bounds__(256, 1) void WG_SKINNY_KERNEL16(SkinnyArgs g) {
                 float4 v = make_float4(acc16[t][0], acc16[t][1], acc16[t][2], acc16[t][3]);
                 if constexpr (F16) {
                     if (!direct) { put4(col, row, v); continue; } // f32 partial slab
+#ifdef WG_GEMM16_OUT32
+                    float *dst = g.c + z * g.c_batch + (uint64_t)col * g.ldc + row; // (an f32 result: no rounding step)
+                    if (g.alpha != 1.f) { v.x *= g.alpha; v.y *= g.alpha; v.z *= g.alpha; v.w *= g.alpha; }
+                    if (g.beta != 0.f) {
+                        const float4 o = wg_ld_u(dst);
+                        v.x = fmaf(g.beta, o.x, v.x); v.y = fmaf(g.beta, o.y, v.y); v.z = fmaf(g.beta, o.z, v.z); v.w = fmaf(g.beta, o.w, v.w);
+                    }
+                    wg_st_u(dst, v);
+#else
                     sk_16 *dst = reinterpret_cast<sk_16 *>(g.c) + z * g.c_batch + (uint64_t)col * g.ldc + row;
                     if (g.alpha != 1.f) { v.x *= g.alpha; v.y *= g.alpha; v.z *= g.alpha; v.w *= g.alpha; }
                     if (g.beta != 0.f) {
@@ -367,6 +380,7 @@ __global__ __launch_bounds__(256, 1) void WG_SKINNY_KERNEL16(SkinnyArgs g) {
                     }
                     const sk_h4 hv = { (sk_16)v.x, (sk_16)v.y, (sk_16)v.z, (sk_16)v.w };
                     *reinterpret_cast<sk_h4 *>(dst) = hv;
+#endif
                 } else put4(col, row, v);
             }
         }
@@ -401,7 +415,7 @@ __global__ __launch_bounds__(256, 1) void WG_SKINNY_KERNEL16(SkinnyArgs g) {
 
 } // namespace
 
-#ifndef WG_GEMM16_BF16
+#if !defined(WG_GEMM16_BF16) && !defined(WG_GEMM16_OUT32)
 // out = alpha * op(m1) * m2 + beta * out on the few-column kernel. Launch only: the caller's plan (gemm32_plan.hip: gemm32_plan / gemm32_skinny_plan) has checked
 // applicability and chose the panels and the K cut -- p.nsplit splits of p.k_per_split; the f32 slabs and their reduce are this function's.
 int wgk_gemm_f32_skinny(wg_ctx *ctx, const wg_gemm32_plan &p, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
@@ -437,12 +451,12 @@ int wgk_gemm_f32_skinny(wg_ctx *ctx, const wg_gemm32_plan &p, bool trans, uint32
     return wg_splitk_reduce(ctx, g.part, ns, M, N, nmats, WG_F32, out, out_ld, out_batch, alpha, beta);
 }
 
-#endif // !WG_GEMM16_BF16
+#endif // the f32 launcher: in the f16 build only
 
 // f16 GemmTr with N <= 16 (f16 GemvTr with a few right-hand sides arrives here through wgk_gemm_f16): out = alpha * m1^T * m2 + beta * out, m1 stored K x M and m2
 // K x N, both k-contiguous. The caller (wgk_gemm_f16, by its plan: gemm16_plan.hip) has checked: K % 8 == 0, leading dimensions % 8 == 0, 16-byte aligned bases,
 // 32-bit offsets in range; it chose the K cut (ns splits of kps), owns the f32 slabs (`part`, ns > 1) and reduces them.
-int WG16_SYM(wgk_gemm_, _skinny)(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_ext_t *out,
+int WG16_SYM(wgk_gemm_, _skinny)(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg16_oext_t *out,
                         uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
                         float alpha, float beta, uint32_t ns, uint32_t kps, float *part) {
     const uint32_t row_blocks = (M + 127u) / 128u;

@@ -238,6 +238,18 @@ int wgk_gemm_f16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, ui
 int wgk_gemm_bf16(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
                   wg_bf16 *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha = 1.f, float beta = 0.f,
                   const wgk_panels *panels = nullptr);
+// wg_gemm_out32 (gemm_f16o32*.hip / gemm_bf16o32*.hip: the same sources compiled with an f32 output element): m1 / m2 hold f16 / bf16, `out` f32; out_ld / out_batch in
+// f32 elements. The 16-bit planner's plan for the same query without the continuous walk; no paneled form.
+int wgk_gemm_f16o32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
+                    float *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha = 1.f, float beta = 0.f,
+                    const wgk_panels *panels = nullptr);
+int wgk_gemm_bf16o32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
+                     float *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha = 1.f, float beta = 0.f,
+                     const wgk_panels *panels = nullptr);
+int wgk_gemm_f16o32_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
+                           float alpha, float beta, uint32_t ns, uint32_t kps, float *part);
+int wgk_gemm_bf16o32_skinny(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2,
+                            float alpha, float beta, uint32_t ns, uint32_t kps, float *part);
 int wgk_gemm_bf16_nt(wg_ctx *ctx, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats, wg_bf16 *out, uint32_t out_ld, uint64_t out_batch, wgk_mat a_mcontig, wgk_mat b_ncontig,
                      float alpha = 1.f, float beta = 0.f);
 // gemm_f16_nt.hip: out (M x N, column-major) = a (M x K, m-contiguous: ld between k) * b (K x N, N-CONTIGUOUS: element (k, n) at n + k * ld) -- the row-major GemmTr in

@@ -67,6 +67,14 @@ def _mixed_dtype(out: GpuTensorView, m: GpuTensorView, v: GpuTensorView) -> int:
     return md
 
 
+def _out32_dtype(out: GpuTensorView, m1: GpuTensorView, m2: GpuTensorView) -> int:
+    """The operands' wg_dtype of an f32-output Gemm: `m1` and `m2` share float16 / bfloat16 / float32, `out` is float32 -- anything else is a TypeError."""
+    dt = _common_dtype(m1, m2)
+    if np.dtype(out._tensor.dtype) != np.dtype(np.float32):
+        raise TypeError(f"f32-output Gemm: `out` must be float32, got {out._tensor.dtype} (`m1` and `m2` carry the 16-bit type)")
+    return dt
+
+
 def row_major_shader_defs() -> dict:
     """linalg/shape.rs:11-15: the shader definitions that switch `Shape` to row-major.  Pass them to `Gemm.from_device` /
     `Gemv.from_device` (the reference passes them to the shader composer) to get operators whose matrix views are row-major."""
@@ -112,6 +120,26 @@ class Gemm:
         check(lib.wg_gemm_ex(pass_._ctx.handle, int(variant), dt, float(alpha), float(beta),
                              out.buffer()._h, out.shape().to_c(), m1.buffer()._h, m1.shape().to_c(),
                              m2.buffer()._h, m2.shape().to_c()))
+
+
+    def dispatch_out32(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m1, m2) -> None:
+        self.dispatch_out32_generic(device, shapes, pass_, out, m1, m2, GemmVariant.Gemm)
+
+    def dispatch_out32_tr(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m1, m2) -> None:
+        self.dispatch_out32_generic(device, shapes, pass_, out, m1, m2, GemmVariant.GemmTr)
+
+    def dispatch_out32_generic(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m1, m2, variant: GemmVariant,
+                               alpha: float = 1.0, beta: float = 0.0) -> None:
+        """Extension (`wg_gemm_out32`): float16 / bfloat16 `m1` and `m2` with a float32 `out` = alpha * op(m1) * m2 + beta * out. The f32 accumulators of the
+        16-bit Gemm are stored as they are (no 16-bit rounding anywhere); float32 operands are `dispatch_ex`. Column-major views only (the row-major surface
+        has no f32-output form)."""
+        out, m1, m2 = as_view(out, 3), as_view(m1, 3), as_view(m2, 3)
+        dt = _out32_dtype(out, m1, m2)
+        if self.row_major:
+            raise TypeError("Gemm.dispatch_out32*: the row-major operator surface has no f32-output form")
+        check(lib.wg_gemm_out32(pass_._ctx.handle, int(variant), dt, float(alpha), float(beta),
+                                out.buffer()._h, out.shape().to_c(), m1.buffer()._h, m1.shape().to_c(),
+                                m2.buffer()._h, m2.shape().to_c()))
 
 
 class Gemv:
