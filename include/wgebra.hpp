@@ -465,6 +465,21 @@ struct Gemv {
     void dispatch_mixed_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<W> m, GpuTensorView<float> v) const {
         dispatch_mixed_generic(d, s, p, out, m, v, GemvVariant::GemvTr);
     }
+    // extension (wg_gemv_q8): int8 weights with one f32 scale per group_rows consecutive rows of a column (scales: ceil(rows / group_rows) x cols x mats), f32 vectors
+    // and an f32 result -- out = W v or W^T v with W = scales[r / group_rows, c] * m[r, c]. Column-major views (the row-major surface has no q8 form).
+    void dispatch_q8_generic(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<float> out, GpuTensorView<int8_t> m, GpuTensorView<float> scales,
+                             GpuTensorView<float> v, uint32_t group_rows, GemvVariant variant = GemvVariant::Gemv) const {
+        check(wg_gemv_q8(pass.ctx(), (wg_gemv_variant)variant, group_rows, out.buffer(), out.shape(), m.buffer(), m.shape(), scales.buffer(), scales.shape(), v.buffer(),
+                         v.shape()));
+    }
+    void dispatch_q8(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<int8_t> m, GpuTensorView<float> scales,
+                     GpuTensorView<float> v, uint32_t group_rows) const {
+        dispatch_q8_generic(d, s, p, out, m, scales, v, group_rows, GemvVariant::Gemv);
+    }
+    void dispatch_q8_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<int8_t> m, GpuTensorView<float> scales,
+                        GpuTensorView<float> v, uint32_t group_rows) const {
+        dispatch_q8_generic(d, s, p, out, m, scales, v, group_rows, GemvVariant::GemvTr);
+    }
 };
 
 // reduce.rs:62-113

@@ -54,6 +54,7 @@ extern "C" {
                                     wg_timestamps_write_at, WG_TUNE_RM_TR_NATIVE, wg_debug_gemm16_plan and wg_debug_gemm32_plan (added diagnostic symbols with their two structs each); WG_ERR_ALIASED = 9 (an appended status: calls that
                                     return it used to launch kernels that raced on their own operands) with wg_debug_views_overlap; and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
                                     that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump); wg_gemv_mixed (an added symbol); wg_gemm_out32 with wg_debug_gemm_out32_query (added symbols);
+                                    wg_gemv_q8 with wg_debug_gemv_q8_plan and its two structs (added symbols; wg_dtype is unchanged);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
 
@@ -351,6 +352,40 @@ typedef struct wg_gemm32_plan {
  * few-row plan the tag string goes on with the transposes and the inner call's tags. inner (may be NULL): the query of that inner call (few-row plans only; else a
  * copy of `query`). */
 int wg_debug_gemm32_plan(const wg_gemm32_query *query, wg_gemm32_plan *plan, char *tags, size_t cap, wg_gemm32_query *inner);
+/* The same for wg_gemv_q8's launcher (gemv_q8_plan.hip): kernel, right-hand-side tile, cut of the contraction, grid and workspace bytes as a pure function of
+ * the query. Sizes and strides count each operand's own elements (1 byte for `m`, 4 bytes for the others); *_addr16: the byte address of the view's first
+ * element modulo 16. */
+typedef struct wg_gemv_q8_query {
+    uint32_t trans;                          /* 0: out = W v (Gemv, GemvFast); 1: out = W^T v (GemvTr, GemvTrFast) */
+    uint32_t rows, cols, nrhs, mats;         /* the matrix as stored (rows x cols); right-hand sides and matrices (taken from `out`) */
+    uint32_t group_rows;                     /* as passed: a positive multiple of 16, or any value >= rows */
+    uint32_t ldm, lds, ldv, ldo;             /* leading dimensions of m, scales, v and out */
+    uint64_t m_batch, s_batch, v_batch, o_batch; /* matrix strides */
+    uint32_t m_addr16, v_addr16, o_addr16;   /* byte address of the first element of m, v and out, modulo 16 (scales are read 4 bytes at a time: any view) */
+    uint32_t cus;                            /* compute units of the context's stream */
+} wg_gemv_q8_query;
+typedef enum wg_gemv_q8_leaf {
+    WG_GEMV_Q8_NOTHING = 0,      /* no output element: no launch, WG_OK */
+    WG_GEMV_Q8_UNSUPPORTED = 1,  /* no launch: the call returns `status` with `message` */
+    WG_GEMV_Q8_T = 2,            /* out = W^T v, a half-wave per column or per 4 adjacent columns, 16-byte loads (gemv_q8_t_kernel) */
+    WG_GEMV_Q8_N = 3,            /* out = W v, 16 rows per lane, 16-byte loads (gemv_q8_n_kernel) */
+    WG_GEMV_Q8_ANY_T = 4,        /* out = W^T v element by element: any view */
+    WG_GEMV_Q8_ANY_N = 5         /* out = W v element by element: any view */
+} wg_gemv_q8_leaf;
+typedef struct wg_gemv_q8_plan {
+    uint32_t leaf;                           /* wg_gemv_q8_leaf */
+    uint32_t rhs_tile, rhs_groups;           /* right-hand sides per pass over the matrix in registers (1, 2, 4, 8); groups of 8 right-hand sides on grid.z */
+    uint32_t loads, cols;                    /* WG_GEMV_Q8_T: 16-byte loads in flight per lane and column (a trip is 512 * loads rows) and adjacent columns per half-wave (1 or 4:
+                                                they share the vectors' pieces); WG_GEMV_Q8_N: columns in flight per lane, 1 */
+    uint32_t nsplit, k_per_split;            /* cut of the contraction over grid.y (1, k: none); no empty split, every boundary a multiple of 16 */
+    uint32_t out_per_block;                  /* outputs a workgroup owns: block b takes [b * out_per_block, (b + 1) * out_per_block) */
+    uint32_t grid[3], block;                 /* the launch: grid = (output blocks, splits, mats * rhs_groups) */
+    uint64_t workspace_bytes;                /* f32 partials of a cut: mats * nsplit * nrhs * outputs * 4 (the context's workspace), 0 without a cut */
+    int32_t status;                          /* WG_GEMV_Q8_NOTHING / _UNSUPPORTED */
+    char message[128];
+} wg_gemv_q8_plan;
+/* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the combine pass of a cut included. */
+int wg_debug_gemv_q8_plan(const wg_gemv_q8_query *query, wg_gemv_q8_plan *plan, char *tags, size_t cap);
 int wg_ctx_get_tuning(const wg_ctx *ctx, wg_tuning key, int *value);
 /* Diagnostics / tests (no context, no device): the predicate behind WG_ERR_ALIASED. Returns 1 when the footprints of two views share a byte, 0 when they do not.
  * byte_base_*: the byte address of element 0 of the buffer each view indexes (wg_buf_device_ptr; any integers do, only their difference matters); elem_size: bytes
@@ -467,6 +502,46 @@ int wg_gemv_mixed(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype m_dtype,
                   wg_buf *out, wg_view_shape out_shape,
                   const wg_buf *m, wg_view_shape m_shape,
                   const wg_buf *v, wg_view_shape v_shape);
+
+/*
+ * Extension: Gemv on 8-bit weights with group scales -- an int8_t matrix, f32 scales, f32 vectors and an f32 result (the decode step on weights stored as in Q8_0 or
+ * per-channel int8: half the bytes of the 16-bit wg_gemv_mixed). The matrix is W[r, c, z] = scales[r / G, c, z] * (float)m[r, c, z] with G = group_rows: groups run
+ * along the matrix's ROWS, the contiguous dimension, for every variant (GemvTr on weights stored k x outputs: a group is group_rows consecutive weights of one
+ * output). out = W v (WG_GEMV, WG_GEMV_FAST) or W^T v (WG_GEMV_TR, WG_GEMV_TR_FAST), for every right-hand side and matrix of `out`; no alpha, no beta: wg_gemv's product.
+ * `m` holds int8_t (all 256 values are legal, -128 included), column-major like every view; `scales` holds f32, ceil(m.rows / group_rows) x m.cols x m.mats; `v` and
+ * `out` hold f32. Every view shape counts elements of its own operand's type; the bounds checks use 1 byte for `m` and 4 bytes for the others. wg_dtype has no 8-bit
+ * value and gets none: no other entry point reads 1-byte elements.
+ *   group_rows    : a positive multiple of 16, or any positive value >= m.rows (one scale per column: `scales` has one row). Anything else is WG_ERR_INVALID_ARG.
+ *   DIM_MISMATCH  : wg_gemv's two checks with its message; then `scales` of another shape than the one above ("Gemv: dimension mismatch. (m [..], group_rows G,
+ *                   scales [..], expected [..])").
+ * Everything else is wg_gemv_mixed's contract, in its order, with its status codes and messages: the NULL context ("Gemv: ctx is NULL"), NULL buffers, the unknown
+ * variant, *_FAST with out rows % 4 != 0 (PRECONDITION), WG_GEMV_TR_FAST falling back to WG_GEMV_TR, zero-sized buffers / views skipped with WG_OK, right-hand sides
+ * and batch taken from `out`, views that exceed their buffer, nmats * ceil(nrhs / 8) > 65535 (UNSUPPORTED), WG_ERR_WORKSPACE when the partials of a cut contraction
+ * would have to grow the context's workspace inside a recording.
+ * Arithmetic:
+ *   - int8 is widened exactly; `v` and `scales` are read as the f32 they are and never narrowed; every operation is an f32 FMA or multiply; the f32 accumulator is
+ *     stored as it is. Nothing is flushed: subnormal scales, vector entries and results are kept.
+ *   - where the scale enters (the kernel's choice; each of the k terms takes at most two f32 roundings either way):
+ *       GemvTr, aligned views (gemv_q8_t_kernel): per 16-weight PIECE -- d = sum of the piece's 16 products q * v (sequential FMAs from zero), then
+ *         acc = fmaf(scale, d, acc). A piece never straddles a group. The unscaled d must be finite for a finite result (|q| <= 128: no concern below 1e35);
+ *       Gemv, aligned views (gemv_q8_n_kernel): per column and 16-row piece into the VECTOR entry -- t = scale * v[c], then acc[r] = fmaf(q, t, acc[r]);
+ *       any other view (the element-by-element kernels): per ELEMENT -- w = scale * q (the dequantised weight), then acc = fmaf(w, v, acc).
+ *   - Inf and NaN behave as in the f32 product of the dequantised matrix with `v`: 0 * Inf is NaN (a zero scale against an Inf in `v`, a zero weight against it),
+ *     and a NaN reaches exactly the outputs whose sums contain it; load slots past the end of a range contribute nothing. `out` is overwritten.
+ *   - deterministic: no atomics; a cut contraction writes f32 partials that one pass adds in a fixed order -- two calls give identical bits.
+ * Which kernels (gemv_q8_plan.hip, wg_debug_gemv_q8_plan): the two streaming kernels take views where m.rows % 16 == 0, the matrix's first element, leading dimension
+ * and matrix stride are multiples of 16 bytes, and the operand the kernel reaches with float4 accesses -- `v` for GemvTr, `out` for Gemv -- is vec4-aligned (address, leading
+ * dimension and matrix stride multiples of 16 bytes where they count; the other one is reached one float at a time and may be any view); every other view runs where it lies on the element-by-element kernels -- correct, not fast, and without any copy of the matrix. Up to 8 right-hand sides share one
+ * pass over the matrix; more run as groups of 8 on grid.z.
+ *   ALIASED       : `out` shares a byte with the part of `m`, of `scales` or of `v` the call addresses -- on addresses, `out` against `m` in 1-byte units, so both may
+ *                   live in one buffer: touching is legal, one shared byte is refused. The read operands may overlap each other.
+ * wg_debug_take_path: tags begin "gemv_q8/": "gemv_q8/t,nr=1,u=2,c=4,ns=1" (right-hand-side tile, loads in flight per column, columns per half-wave, splits), "gemv_q8/n,nr=8,u=8,ns=4", "gemv_q8/combine,ns=4", "gemv_q8/any_t", "gemv_q8/any_n".
+ */
+int wg_gemv_q8(wg_ctx *ctx, wg_gemv_variant variant, uint32_t group_rows,
+               wg_buf *out, wg_view_shape out_shape,             /* f32 */
+               const wg_buf *m, wg_view_shape m_shape,           /* int8_t, column-major like every view */
+               const wg_buf *scales, wg_view_shape scales_shape, /* f32: ceil(m.rows / group_rows) x m.cols x mats */
+               const wg_buf *v, wg_view_shape v_shape);          /* f32 */
 
 /*
  * Extension: Gemm on 16-bit operands with an f32 result -- out = alpha * op(m1) * m2 + beta * out with the f32 accumulators of the matrix cores stored as they

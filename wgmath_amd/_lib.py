@@ -73,6 +73,23 @@ class Gemm32PlanC(ctypes.Structure):
                 + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
 
 
+class GemvQ8QueryC(ctypes.Structure):
+    """wg_gemv_q8_query: everything wg_gemv_q8's choice of kernel, cut and grid depends on (wg_debug_gemv_q8_plan)."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("trans", "rows", "cols", "nrhs", "mats", "group_rows", "ldm", "lds", "ldv", "ldo")]
+                + [(n, ctypes.c_uint64) for n in ("m_batch", "s_batch", "v_batch", "o_batch")]
+                + [(n, ctypes.c_uint32) for n in ("m_addr16", "v_addr16", "o_addr16", "cus")])
+
+
+GEMV_Q8_LEAVES = ("nothing", "unsupported", "t", "n", "any_t", "any_n")  # wg_gemv_q8_leaf
+
+
+class GemvQ8PlanC(ctypes.Structure):
+    """wg_gemv_q8_plan: the leaf (index into GEMV_Q8_LEAVES) and what it is launched with."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("leaf", "rhs_tile", "rhs_groups", "loads", "cols", "nsplit", "k_per_split", "out_per_block")]
+                + [("grid", ctypes.c_uint32 * 3), ("block", ctypes.c_uint32), ("workspace_bytes", ctypes.c_uint64)]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
+
+
 class WgError(RuntimeError):
     """A non-OK wg_status.  `.status` is the code, the message is wg_last_error_string()."""
 
@@ -159,6 +176,8 @@ def _load() -> ctypes.CDLL:
         "wg_gemm_ex": (ci, [vp, ci, ci, ctypes.c_float, ctypes.c_float, vp, S, vp, S, vp, S]),
         "wg_gemv": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),
         "wg_gemv_mixed": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),
+        "wg_gemv_q8": (ci, [vp, ci, u32, vp, S, vp, S, vp, S, vp, S]),
+        "wg_debug_gemv_q8_plan": (ci, [ctypes.POINTER(GemvQ8QueryC), ctypes.POINTER(GemvQ8PlanC), cp, sz]),
         "wg_gemm_out32": (ci, [vp, ci, ci, ctypes.c_float, ctypes.c_float, vp, S, vp, S, vp, S]),
         "wg_debug_gemm_out32_query": (ci, [ctypes.POINTER(Gemm16QueryC)]),
         "wg_gemm_rm": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),

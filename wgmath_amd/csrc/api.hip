@@ -4,6 +4,7 @@
 // kernels ever run: a view that is written must not share memory with a view the same call reads (check_alias; the rule: include/wgebra_hip.h).
 #include "wg_internal.hpp"
 #include "views_overlap.hpp"
+#include "gemv_q8_plan.hpp"
 
 namespace {
 
@@ -18,13 +19,15 @@ inline uint64_t extent(const View &v) {
     return (uint64_t)(v.mats - 1) * v.stride_mat + v.offset + (uint64_t)(v.rows - 1) + (uint64_t)(v.cols - 1) * v.stride + 1;
 }
 
-int check_bounds(const char *op, const char *name, const View &v, const wg_buf *b, wg_dtype dt) {
-    const uint64_t need = extent(v), have = b->bytes / wg_dtype_size(dt);
+// (es: bytes per element -- wg_dtype_size(dt) below; wg_gemv_q8 passes the 1 of its int8 matrix, which no wg_dtype names)
+int check_bounds_es(const char *op, const char *name, const View &v, const wg_buf *b, size_t es) {
+    const uint64_t need = extent(v), have = b->bytes / es;
     if (need > have)
         return wg_set_error(WG_ERR_OUT_OF_BOUNDS, "%s: view `%s` addresses %llu elements but its buffer holds %llu", op, name,
                             (unsigned long long)need, (unsigned long long)have);
     return WG_OK;
 }
+int check_bounds(const char *op, const char *name, const View &v, const wg_buf *b, wg_dtype dt) { return check_bounds_es(op, name, v, b, wg_dtype_size(dt)); }
 
 // The aliasing rule (include/wgebra_hip.h): the written view `w` of a call must not share a byte with a view `r` it reads. Asked after the bounds checks and before
 // anything is launched or logged, on the views the call really addresses (the ones check_bounds gets) and on addresses -- base_*: element 0 of each view's buffer --,
@@ -49,6 +52,12 @@ int check_alias(const char *op, wg_dtype dt, const char *wname, const View &w, c
 int check_alias_f32_u16(const char *op, const char *wname, const View &w, const void *base_w, const char *rname, const View &r, const void *base_r) {
     int exact = 1;
     if (!wg_views_overlap_f32_u16(shape_of(w), (uint64_t)(uintptr_t)base_w, shape_of(r), (uint64_t)(uintptr_t)base_r, &exact)) return WG_OK;
+    return aliased(op, wname, rname, exact);
+}
+// ... and against a read view of 1-byte elements (wg_gemv_q8: `out` and the int8 matrix): in 1-byte units
+int check_alias_f32_u8(const char *op, const char *wname, const View &w, const void *base_w, const char *rname, const View &r, const void *base_r) {
+    int exact = 1;
+    if (!wg_views_overlap_f32_u8(shape_of(w), (uint64_t)(uintptr_t)base_w, shape_of(r), (uint64_t)(uintptr_t)base_r, &exact)) return WG_OK;
     return aliased(op, wname, rname, exact);
 }
 inline View one_element() { return View{ 1, 1, 1, 1, 1, 0 }; } // the result scalar of a Reduce: element 0 of its buffer
@@ -401,6 +410,59 @@ int wg_gemv_mixed(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype m_dtype, wg_buf
     wgk_mat M = { elem_ptr(m, mm.offset, m_dtype), mm.stride, mm.stride_mat };
     wgk_mat V = { elem_ptr(v, vv.offset, WG_F32), vv.stride, vv.stride_mat };
     return wgk_gemv_mixed(ctx, tr, m_dtype, o.rows, m_cols, o.cols, o.mats, (float *)elem_ptr(out, o.offset, WG_F32), o.stride, o.stride_mat, M, V);
+}
+
+// wg_gemv on an int8 matrix with f32 group scales (include/wgebra_hip.h): wg_gemv_mixed's checks in its order with its messages, the checks of group_rows and of the
+// scales' shape behind the dimension check; bounds with 1 byte per element of `m`; `out` against `m` in 1-byte units. The kernels are the plan's (gemv_q8_plan.hip).
+int wg_gemv_q8(wg_ctx *ctx, wg_gemv_variant variant, uint32_t group_rows, wg_buf *out, wg_view_shape out_shape, const wg_buf *m, wg_view_shape m_shape, const wg_buf *scales,
+               wg_view_shape scales_shape, const wg_buf *v, wg_view_shape v_shape) {
+    const wg_buf *bufs[4] = { out, m, scales, v };
+    if (int rc = check_common("Gemv", ctx, WG_F32, bufs, 4)) return rc;
+    if ((int)variant < 0 || (int)variant > 3) return wg_set_error(WG_ERR_INVALID_ARG, "Gemv: unknown variant %d", (int)variant);
+    const bool tr = variant == WG_GEMV_TR || variant == WG_GEMV_TR_FAST;
+    const View o = mk(out_shape), mm = mk(m_shape), ss = mk(scales_shape), vv = mk(v_shape);
+
+    const uint32_t m_rows = tr ? mm.cols : mm.rows, m_cols = tr ? mm.rows : mm.cols;
+    if (m_cols != vv.rows || m_rows != o.rows)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemv: dimension mismatch. (out [%u,%u,%u], m [%u,%u,%u]%s, v [%u,%u,%u])", o.rows,
+                            o.cols, o.mats, mm.rows, mm.cols, mm.mats, tr ? "^T" : "", vv.rows, vv.cols, vv.mats);
+    if (group_rows == 0 || (group_rows % 16u != 0 && group_rows < mm.rows))
+        return wg_set_error(WG_ERR_INVALID_ARG, "Gemv: group_rows %u is neither a positive multiple of 16 nor at least the %u rows of m", group_rows, mm.rows);
+    const uint32_t s_rows = mm.rows / group_rows + (mm.rows % group_rows != 0);
+    if (ss.rows != s_rows || ss.cols != mm.cols || ss.mats != mm.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemv: dimension mismatch. (m [%u,%u,%u], group_rows %u, scales [%u,%u,%u], expected [%u,%u,%u])", mm.rows, mm.cols, mm.mats,
+                            group_rows, ss.rows, ss.cols, ss.mats, s_rows, mm.cols, mm.mats);
+    if (variant == WG_GEMV_TR_FAST && mm.rows % 128u != 0) variant = WG_GEMV_TR;
+    if ((variant == WG_GEMV_FAST || variant == WG_GEMV_TR_FAST) && o.rows % 4u != 0)
+        return wg_set_error(WG_ERR_PRECONDITION, "Gemv: assertion `left == right` failed (out_nrows %% 4 == 0, gemv.rs:122): out has %u rows",
+                            o.rows);
+    if (out->bytes == 0 || m->bytes == 0 || scales->bytes == 0 || v->bytes == 0) return WG_OK;
+    if (o.rows == 0 || o.cols == 0 || o.mats == 0) return WG_OK;
+
+    const View m_eff = { mm.rows, mm.cols, o.mats, mm.stride, mm.stride_mat, mm.offset };
+    const View s_eff = { ss.rows, ss.cols, o.mats, ss.stride, ss.stride_mat, ss.offset };
+    const View v_eff = { vv.rows, o.cols, o.mats, vv.stride, vv.stride_mat, vv.offset };
+    if (int rc = check_bounds("Gemv", "out", o, out, WG_F32)) return rc;
+    if (int rc = check_bounds_es("Gemv", "m", m_eff, m, 1)) return rc;
+    if (int rc = check_bounds("Gemv", "scales", s_eff, scales, WG_F32)) return rc;
+    if (int rc = check_bounds("Gemv", "v", v_eff, v, WG_F32)) return rc;
+    if (int rc = check_alias_f32_u8("Gemv", "out", o, out->ptr, "m", m_eff, m->ptr)) return rc;
+    if (int rc = check_alias("Gemv", WG_F32, "out", o, out->ptr, "scales", s_eff, scales->ptr)) return rc;
+    if (int rc = check_alias("Gemv", WG_F32, "out", o, out->ptr, "v", v_eff, v->ptr)) return rc;
+
+    const wgk_mat M = { (const char *)m->ptr + mm.offset, mm.stride, mm.stride_mat };
+    const wgk_mat S = { elem_ptr(scales, ss.offset, WG_F32), ss.stride, ss.stride_mat };
+    const wgk_mat V = { elem_ptr(v, vv.offset, WG_F32), vv.stride, vv.stride_mat };
+    float *O = (float *)elem_ptr(out, o.offset, WG_F32);
+    wg_gemv_q8_query q = {};
+    q.trans = tr; q.rows = mm.rows; q.cols = mm.cols; q.nrhs = o.cols; q.mats = o.mats; q.group_rows = group_rows;
+    q.ldm = mm.stride; q.lds = ss.stride; q.ldv = vv.stride; q.ldo = o.stride;
+    q.m_batch = mm.stride_mat; q.s_batch = ss.stride_mat; q.v_batch = vv.stride_mat; q.o_batch = o.stride_mat;
+    q.m_addr16 = (uint32_t)((uintptr_t)M.ptr % 16u); q.v_addr16 = (uint32_t)((uintptr_t)V.ptr % 16u); q.o_addr16 = (uint32_t)((uintptr_t)O % 16u);
+    q.cus = (uint32_t)wg_ctx_cus(ctx);
+    const wg_gemv_q8_plan p = gemv_q8_plan(q);
+    WG_HIP_TRY(hipSetDevice(ctx->device));
+    return wgk_gemv_q8(ctx, p, tr, group_rows, mm.rows, mm.cols, o.cols, o.mats, O, o.stride, o.stride_mat, M, S, V);
 }
 
 int wg_reduce(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype, const wg_buf *value, wg_view_shape value_shape, wg_buf *result) {

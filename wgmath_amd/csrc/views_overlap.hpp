@@ -44,3 +44,28 @@ inline int wg_views_overlap_f32_u16(const wg_view_shape &f32_view, uint64_t byte
     if (exact) *exact = 0;
     return 1;
 }
+
+// ... and an f32 view against a view of 1-BYTE elements (wg_gemv_q8: an f32 `out` against the int8 matrix, possibly in one buffer): both are compared in 1-byte units.
+// The f32 view with rows, stride and stride_mat scaled by 4 -- and its offset folded into the byte base -- has the same footprint as a view of 1-byte elements, and
+// the exact comparison applies with elem_size 1. A scaled field that leaves 32 bits (an f32 view of 2^30 rows and more, or strides that large where they count) leaves
+// the intervals, as above: disjoint intervals are disjoint footprints, anything else is answered 1 with *exact = 0.
+inline int wg_views_overlap_f32_u8(const wg_view_shape &f32_view, uint64_t byte_base_f32, const wg_view_shape &u8_view, uint64_t byte_base_u8, int *exact) {
+    if (exact) *exact = 1;
+    const wg_view_shape &s = f32_view;
+    if (s.size[0] == 0 || s.size[1] == 0 || s.size[2] == 0) return 0;
+    const uint64_t rows = 4ull * s.size[0], stride = s.size[1] > 1 ? 4ull * s.stride : rows, stride_mat = s.size[2] > 1 ? 4ull * s.stride_mat : 0;
+    const uint64_t base = byte_base_f32 + 4ull * s.offset; // (a device address plus at most 16 GiB: no wrap)
+    if (rows <= 0xffffffffull && stride <= 0xffffffffull && stride_mat <= 0xffffffffull) {
+        const wg_view_shape scaled = { { (uint32_t)rows, s.size[1], s.size[2] }, (uint32_t)stride, (uint32_t)stride_mat, 0 };
+        return wg_views_overlap(scaled, base, u8_view, byte_base_u8, 1, exact);
+    }
+    typedef unsigned __int128 u128;
+    const u128 ext_f = (u128)(s.size[2] - 1) * s.stride_mat + (u128)(s.size[1] - 1) * s.stride + s.size[0]; // f32 elements from the first one on
+    const wg_view_shape &h = u8_view;
+    if (h.size[0] == 0 || h.size[1] == 0 || h.size[2] == 0) return 0;
+    const u128 ext_h = (u128)(h.size[2] - 1) * h.stride_mat + (u128)(h.size[1] - 1) * h.stride + h.size[0];
+    const u128 lo_f = base, hi_f = lo_f + 4 * ext_f, lo_h = (u128)byte_base_u8 + h.offset, hi_h = lo_h + ext_h;
+    if (hi_f <= lo_h || hi_h <= lo_f) return 0;
+    if (exact) *exact = 0;
+    return 1;
+}

@@ -196,6 +196,10 @@ int wgk_gemv_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t rows_out,
                    float *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v);
 int wgk_gemv_any_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
                        wgk_mat m, wgk_mat v);
+// wg_gemv_q8 (gemv_q8.hip): m holds int8_t (rows x cols as stored), s the f32 group scales, v and out f32. Launch only: kernel, right-hand-side tile, cut of the
+// contraction, grid and workspace are the plan's (gemv_q8_plan.hip); ld / batch strides count each operand's own elements.
+int wgk_gemv_q8(wg_ctx *ctx, const wg_gemv_q8_plan &p, bool trans, uint32_t group_rows, uint32_t rows, uint32_t cols, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld,
+                uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat v);
 int wgk_gemv_small_reduce(wg_ctx *ctx, int op, uint32_t rows_out, uint32_t k, float *y, wgk_mat m, wgk_mat v, unsigned *counter, float *result);
 
 int wgk_gemm_f32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,

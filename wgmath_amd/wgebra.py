@@ -67,6 +67,56 @@ def _mixed_dtype(out: GpuTensorView, m: GpuTensorView, v: GpuTensorView) -> int:
     return md
 
 
+def _q8_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView, v: GpuTensorView) -> None:
+    """The element types of a q8 call: `m` int8, `scales`, `v` and `out` float32 -- anything else is a TypeError."""
+    if np.dtype(m._tensor.dtype) != np.dtype(np.int8):
+        raise TypeError(f"q8 Gemv: `m` must be int8, got {m._tensor.dtype}")
+    for name, x in (("scales", scales), ("v", v), ("out", out)):
+        if np.dtype(x._tensor.dtype) != np.dtype(np.float32):
+            raise TypeError(f"q8 Gemv: `{name}` must be float32, got {x._tensor.dtype} (`m` carries the int8 weights)")
+
+
+def _q8_groups(rows: int, group_rows: int) -> int:
+    group_rows = int(group_rows)
+    if group_rows <= 0 or (group_rows % 16 and group_rows < rows):
+        raise ValueError(f"group_rows {group_rows} is neither a positive multiple of 16 nor at least the {rows} rows of the matrix")
+    return group_rows
+
+
+def quantize_q8(w32, group_rows: int):
+    """float32 weights (rows x cols, or rows x cols x mats) -> (q int8, scales float32) in the layout of `Gemv.dispatch_q8*`: groups of `group_rows` consecutive ROWS
+    of a column share a scale (a partial last group; group_rows >= rows: one scale per column). Per group s = fl32(max|w| / 127) and q = clip(rint(w / s), -127, 127)
+    (-128 is never produced); an all-zero group gives s = 0, q = 0. `scales` has ceil(rows / group_rows) rows."""
+    w = np.asarray(w32, np.float32)
+    if w.ndim not in (2, 3):
+        raise ValueError("quantize_q8 takes a matrix (rows x cols) or a cube (rows x cols x mats)")
+    rows = w.shape[0]
+    g = _q8_groups(rows, group_rows)
+    ng = -(-rows // g) if rows else 0
+    q = np.zeros(w.shape, np.int8)
+    scales = np.zeros((ng,) + w.shape[1:], np.float32)
+    for i in range(ng):
+        blk = w[i * g:(i + 1) * g]
+        s = (np.abs(blk).max(axis=0) / np.float32(127)).astype(np.float32)
+        scales[i] = s
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.rint(blk / s)
+        q[i * g:(i + 1) * g] = np.clip(np.where(s == 0, np.float32(0), r), -127, 127).astype(np.int8)
+    return q, scales
+
+
+def dequantize_q8(q, scales, group_rows: int) -> np.ndarray:
+    """The float32 matrix `Gemv.dispatch_q8*` multiplies with: w[r, c] = fl32(scales[r // group_rows, c] * q[r, c])."""
+    q, scales = np.asarray(q), np.asarray(scales, np.float32)
+    if q.dtype != np.dtype(np.int8):
+        raise TypeError(f"dequantize_q8 takes int8 weights, not {q.dtype}")
+    g = _q8_groups(q.shape[0], group_rows)
+    idx = np.arange(q.shape[0]) // g
+    if scales.shape != (-(-q.shape[0] // g) if q.shape[0] else 0,) + q.shape[1:]:
+        raise ValueError(f"scales of shape {scales.shape} do not belong to weights of shape {q.shape} in groups of {g} rows")
+    return (scales[idx] * q.astype(np.float32)).astype(np.float32)
+
+
 def _out32_dtype(out: GpuTensorView, m1: GpuTensorView, m2: GpuTensorView) -> int:
     """The operands' wg_dtype of an f32-output Gemm: `m1` and `m2` share float16 / bfloat16 / float32, `out` is float32 -- anything else is a TypeError."""
     dt = _common_dtype(m1, m2)
@@ -184,6 +234,26 @@ class Gemv:
         check(lib.wg_gemv_mixed(pass_._ctx.handle, int(variant), md,
                                 out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
                                 v.buffer()._h, v.shape().to_c()))
+
+
+    def dispatch_q8(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, v, group_rows: int) -> None:
+        self.dispatch_q8_generic(device, shapes, pass_, out, m, scales, v, group_rows, GemvVariant.Gemv)
+
+    def dispatch_q8_tr(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, v, group_rows: int) -> None:
+        self.dispatch_q8_generic(device, shapes, pass_, out, m, scales, v, group_rows, GemvVariant.GemvTr)
+
+    def dispatch_q8_generic(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, v, group_rows: int,
+                            variant: GemvVariant = GemvVariant.Gemv) -> None:
+        """Extension (`wg_gemv_q8`): an int8 matrix with one float32 scale per `group_rows` consecutive rows of a column (`quantize_q8`'s layout), float32 vectors
+        and a float32 result: out = W v or W^T v with W = scales[r // group_rows, c] * m[r, c]. int8 is widened exactly, nothing is narrowed, sums are f32.
+        Column-major views only (the row-major surface has no q8 form)."""
+        out, m, scales, v = as_view(out, 3), as_view(m, 3), as_view(scales, 3), as_view(v, 3)
+        _q8_dtypes(out, m, scales, v)
+        if self.row_major:
+            raise TypeError("Gemv.dispatch_q8*: the row-major operator surface has no q8 form")
+        check(lib.wg_gemv_q8(pass_._ctx.handle, int(variant), int(group_rows),
+                             out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
+                             scales.buffer()._h, scales.shape().to_c(), v.buffer()._h, v.shape().to_c()))
 
 
 def gemv_reduce(pass_: ComputePass, op: "ReduceOp", result: GpuTensor, m, v, variant: "GemvVariant" = None) -> None:
