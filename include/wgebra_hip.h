@@ -55,6 +55,7 @@ extern "C" {
                                     return it used to launch kernels that raced on their own operands) with wg_debug_views_overlap; and WG_BF16 = 2 in wg_dtype (a new enum value: backward compatible -- every call
                                     that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump); wg_gemv_mixed (an added symbol); wg_gemm_out32 with wg_debug_gemm_out32_query (added symbols);
                                     wg_gemv_q8 with wg_debug_gemv_q8_plan and its two structs (added symbols; wg_dtype is unchanged);
+                                    wg_debug_gemv_plan and wg_debug_gemv_any_plan with wg_gemv_query and their plan structs (added diagnostic symbols);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
 
@@ -386,6 +387,64 @@ typedef struct wg_gemv_q8_plan {
 } wg_gemv_q8_plan;
 /* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the combine pass of a cut included. */
 int wg_debug_gemv_q8_plan(const wg_gemv_q8_query *query, wg_gemv_q8_plan *plan, char *tags, size_t cap);
+/* The same for the launcher of wg_gemv, wg_gemv_mixed and the fused wg_gemv_reduce (gemv_plan.hip): leaf, right-hand-side tile, cut of the contraction, grids and
+ * workspace bytes as a pure function of the query. The query describes the call as the vec4 kernels get it (api.hip: the views as they are, or their staged copies);
+ * sizes and strides count each operand's own elements. */
+typedef struct wg_gemv_query {
+    uint32_t trans;                          /* 0: out = m v (m is rows_out x k); 1: out = m^T v (m is k x rows_out) */
+    uint32_t rows_out, k, nrhs, nmats;       /* outputs per vector, contraction length, right-hand sides, matrices */
+    uint32_t m_elem, v_elem;                 /* bytes per element of the matrix and of the vectors / the result: 2 or 4 (wg_gemv_mixed: 2 and 4) */
+    uint32_t bf16;                           /* the 16-bit elements are bfloat16 (the element prefix of the tags; no decision reads it) */
+    uint32_t gemm16;                         /* the 16-bit-both form (wg_gemv on f16 / bf16): the call may be handed to the 16-bit Gemm kernels */
+    uint32_t ldm, ldv, ldo;                  /* leading dimensions of m, v and out (out's, and its matrix stride, are part of the call; no decision reads them yet) */
+    uint64_t m_batch, v_batch, o_batch;      /* matrix strides */
+    uint32_t m_addr16, v_addr16;             /* byte address of the first element of m and v, modulo 16 (the 16-byte loads of gemv.tcols/e=8) */
+    uint32_t cus;                            /* compute units of the context's stream */
+    int32_t gemvt_lds;                       /* WG_TUNE_GEMVT_LDS */
+} wg_gemv_query;
+typedef enum wg_gemv_leaf {
+    WG_GEMV_NOTHING = 0,        /* no output element: no launch, WG_OK */
+    WG_GEMV_UNSUPPORTED = 1,    /* no launch: the call returns `status` with `message` */
+    WG_GEMV_SMALL = 2,          /* out = m v, launch-bound: one kernel, no partials (gemv_n_small_kernel); the calls the fused Gemv + Reduce takes */
+    WG_GEMV_N = 3,              /* out = m v (gemv_n_kernel) */
+    WG_GEMV_T = 4,              /* out = m^T v, 4 columns per wave (gemv_t_kernel) */
+    WG_GEMV_TCOLS = 5,          /* out = m^T v, a half-wave per column, 1 or 2 vectors (gemv_t_cols_kernel) */
+    WG_GEMV_TLDS = 6,           /* f32 out = m^T v, 2 .. 8 vectors held in the LDS (gemv_t_lds_kernel) */
+    WG_GEMV_AS_GEMM32 = 7,      /* handed to the f32 few-column Gemm kernel: `gemm32` is that call's plan */
+    WG_GEMV_AS_GEMM16 = 8       /* handed to the 16-bit Gemm launcher, which plans the call itself (gemm16_plan.hip) */
+} wg_gemv_leaf;
+typedef struct wg_gemv_plan {
+    uint32_t leaf;                           /* wg_gemv_leaf */
+    uint32_t rhs_tile, rhs_groups;           /* right-hand sides per pass over the matrix in registers (1, 2, 4, 8); groups of 8 right-hand sides on grid.z */
+    uint32_t e, u, v;                        /* WG_GEMV_TCOLS: elements per load (4, or 8: one 16-byte load of 16-bit elements), loads in flight per lane, vectors (1, 2) */
+    uint32_t rl;                             /* WG_GEMV_SMALL: lanes x float4 of rows per workgroup (2, 4, 8) */
+    uint32_t lds_cols, lds_threads;          /* WG_GEMV_TLDS: adjacent columns per half-wave, threads per workgroup, ... */
+    uint32_t lds_kc, lds_bytes;              /* ... contracted rows per LDS chunk (k: one chunk) and the dynamic LDS of a workgroup */
+    uint32_t nsplit, k_per_split;            /* cut of the contraction over grid.y (1, k: none), final: no empty split, every boundary a multiple of 4 */
+    uint32_t grid[3], block;                 /* the launch */
+    uint32_t combine_grid[3];                /* nsplit > 1: the pass that sums the partials (256 threads) */
+    uint64_t workspace_bytes;                /* f32 partials of a cut: nmats * nsplit * nrhs * rows_out * 4 (the context's workspace), 0 without a cut */
+    int32_t status;                          /* WG_GEMV_NOTHING / _UNSUPPORTED */
+    char message[128];
+    wg_gemm32_plan gemm32;                   /* WG_GEMV_AS_GEMM32 */
+} wg_gemv_plan;
+/* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path) from "gemv>" on: the element prefix
+ * ("f32.gemv", "f16.gemv", "bf16.gemv", "f16w.gemv", "bf16w.gemv") where the launcher logs one, the leaf and the combine pass; for WG_GEMV_AS_GEMM32 the tags of the
+ * few-column plan; for WG_GEMV_AS_GEMM16 "gemv>" alone (what follows is wg_debug_gemm16_plan's). */
+int wg_debug_gemv_plan(const wg_gemv_query *query, wg_gemv_plan *plan, char *tags, size_t cap);
+/* ... and for the any-alignment kernels (gemv_any.hip) on the same query (it reads trans, rows_out, k, nrhs, nmats, m_elem and cus): the (matrix, right-hand side)
+ * pairs go over grid.z in chunks of `zchunk`, each with its own combine pass. */
+typedef struct wg_gemv_any_plan {
+    uint32_t launch;                         /* 0: nothing to do (status WG_OK) or refused (`status`, `message`) */
+    uint32_t nsplit, per_split;              /* cut of the contraction over grid.y: whole 64-column chunks (N) / whole 64-lane row steps (T) per split */
+    uint32_t grid_x, zchunk, nchunks;        /* output blocks; pairs per launch (<= 65535) and launches */
+    uint32_t nt;                             /* the matrix is read with the non-temporal hint */
+    uint64_t workspace_bytes;                /* f32 partials of one chunk: zchunk * nsplit * rows_out * 4, 0 without a cut */
+    int32_t status;
+    char message[128];
+    char tag[48];                            /* "gemv_any/n,ns=4", "gemv_any/t,ns=1,chunks=2" */
+} wg_gemv_any_plan;
+int wg_debug_gemv_any_plan(const wg_gemv_query *query, wg_gemv_any_plan *plan, char *tags, size_t cap);
 int wg_ctx_get_tuning(const wg_ctx *ctx, wg_tuning key, int *value);
 /* Diagnostics / tests (no context, no device): the predicate behind WG_ERR_ALIASED. Returns 1 when the footprints of two views share a byte, 0 when they do not.
  * byte_base_*: the byte address of element 0 of the buffer each view indexes (wg_buf_device_ptr; any integers do, only their difference matters); elem_size: bytes

@@ -90,6 +90,29 @@ class GemvQ8PlanC(ctypes.Structure):
                 + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
 
 
+class GemvQueryC(ctypes.Structure):
+    """wg_gemv_query: everything the Gemv launchers' choice of kernel, cut and grid depends on (wg_debug_gemv_plan, wg_debug_gemv_any_plan)."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("trans", "rows_out", "k", "nrhs", "nmats", "m_elem", "v_elem", "bf16", "gemm16", "ldm", "ldv", "ldo")]
+                + [(n, ctypes.c_uint64) for n in ("m_batch", "v_batch", "o_batch")]
+                + [(n, ctypes.c_uint32) for n in ("m_addr16", "v_addr16", "cus")] + [("gemvt_lds", ctypes.c_int32)])
+
+
+GEMV_LEAVES = ("nothing", "unsupported", "small", "n", "t", "tcols", "tlds", "as_gemm32", "as_gemm16")  # wg_gemv_leaf
+
+
+class GemvPlanC(ctypes.Structure):
+    """wg_gemv_plan: the leaf (index into GEMV_LEAVES) and what it is launched with."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("leaf", "rhs_tile", "rhs_groups", "e", "u", "v", "rl", "lds_cols", "lds_threads", "lds_kc", "lds_bytes", "nsplit", "k_per_split")]
+                + [("grid", ctypes.c_uint32 * 3), ("block", ctypes.c_uint32), ("combine_grid", ctypes.c_uint32 * 3), ("workspace_bytes", ctypes.c_uint64)]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128), ("gemm32", Gemm32PlanC)])
+
+
+class GemvAnyPlanC(ctypes.Structure):
+    """wg_gemv_any_plan: cut, chunks of grid.z, workspace and tag of the any-alignment kernels."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("launch", "nsplit", "per_split", "grid_x", "zchunk", "nchunks", "nt")] + [("workspace_bytes", ctypes.c_uint64)]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128), ("tag", ctypes.c_char * 48)])
+
+
 class WgError(RuntimeError):
     """A non-OK wg_status.  `.status` is the code, the message is wg_last_error_string()."""
 
@@ -178,6 +201,8 @@ def _load() -> ctypes.CDLL:
         "wg_gemv_mixed": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),
         "wg_gemv_q8": (ci, [vp, ci, u32, vp, S, vp, S, vp, S, vp, S]),
         "wg_debug_gemv_q8_plan": (ci, [ctypes.POINTER(GemvQ8QueryC), ctypes.POINTER(GemvQ8PlanC), cp, sz]),
+        "wg_debug_gemv_plan": (ci, [ctypes.POINTER(GemvQueryC), ctypes.POINTER(GemvPlanC), cp, sz]),
+        "wg_debug_gemv_any_plan": (ci, [ctypes.POINTER(GemvQueryC), ctypes.POINTER(GemvAnyPlanC), cp, sz]),
         "wg_gemm_out32": (ci, [vp, ci, ci, ctypes.c_float, ctypes.c_float, vp, S, vp, S, vp, S]),
         "wg_debug_gemm_out32_query": (ci, [ctypes.POINTER(Gemm16QueryC)]),
         "wg_gemm_rm": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),

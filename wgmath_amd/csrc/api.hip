@@ -5,6 +5,7 @@
 #include "wg_internal.hpp"
 #include "views_overlap.hpp"
 #include "gemv_q8_plan.hpp"
+#include "gemv_plan.hpp"
 
 namespace {
 
@@ -518,22 +519,24 @@ int wg_gemv_reduce(wg_ctx *ctx, wg_gemv_variant variant, wg_reduce_op op, wg_dty
     void *ws = nullptr;
     if (int rc = wg_ctx_tr_workspace(ctx, (size_t)(out_rows ? out_rows : 4) * sizeof(float), &ws)) return rc;
     // Launch-bound sizes (the single-kernel Gemv family): ONE launch -- the last workgroup to finish folds y in the reference order
-    // (gemv.hip, gemv_n_small_reduce_kernel). Same checks as wg_gemv would make; everything else falls through to the two launches.
-    if (!tr && dtype == WG_F32 && mm.cols == vv.rows && out_rows >= 128u && out_rows % 4u == 0 && mm.cols % 4u == 0 && mm.cols > 0 &&
-        m->bytes && v->bytes && mm.offset % 4u == 0 && vv.offset % 4u == 0 && (mm.cols == 1 || mm.stride % 4u == 0) &&
-        (uint64_t)out_rows * mm.cols <= (4ull << 20)) {
-        const View m_eff = { mm.rows, mm.cols, 1, mm.stride, mm.stride_mat, mm.offset }, v_eff = { vv.rows, 1, 1, vv.stride, vv.stride_mat, vv.offset };
-        if (int rc = check_bounds("Gemv", "m", m_eff, m, dtype)) return rc;
-        if (int rc = check_bounds("Gemv", "v", v_eff, v, dtype)) return rc;
-        if (!ctx->flags) {
-            if (ctx->recording) return wg_set_error(WG_ERR_WORKSPACE, "gemv_reduce: arrival counter needed while recording: run the call once outside the recording first");
-            WG_HIP_TRY(hipSetDevice(ctx->device));
-            WG_HIP_TRY(hipMalloc((void **)&ctx->flags, 256));
-            WG_HIP_TRY(hipMemsetAsync(ctx->flags, 0, 256, ctx->stream));
+    // (gemv.hip, gemv_n_small_reduce_kernel) -- for exactly the calls wg_gemv would run on its single-kernel leaf (gemv_plan.hip). Same checks as wg_gemv would make;
+    // everything else falls through to the two launches.
+    if (!tr && dtype == WG_F32 && mm.cols == vv.rows && out_rows % 4u == 0 && mm.cols % 4u == 0 && mm.cols > 0 &&
+        m->bytes && v->bytes && mm.offset % 4u == 0 && vv.offset % 4u == 0 && (mm.cols == 1 || mm.stride % 4u == 0)) {
+        const wgk_mat M = { elem_ptr(m, mm.offset, dtype), mm.stride, mm.stride_mat }, V = { elem_ptr(v, vv.offset, dtype), vv.stride, vv.stride_mat };
+        const wg_gemv_plan p = gemv_plan(wgk_gemv_query(ctx, false, dtype, dtype, false, out_rows, mm.cols, 1, 1, out_rows, out_rows, M, V));
+        if (p.leaf == WG_GEMV_SMALL) {
+            const View m_eff = { mm.rows, mm.cols, 1, mm.stride, mm.stride_mat, mm.offset }, v_eff = { vv.rows, 1, 1, vv.stride, vv.stride_mat, vv.offset };
+            if (int rc = check_bounds("Gemv", "m", m_eff, m, dtype)) return rc;
+            if (int rc = check_bounds("Gemv", "v", v_eff, v, dtype)) return rc;
+            if (!ctx->flags) {
+                if (ctx->recording) return wg_set_error(WG_ERR_WORKSPACE, "gemv_reduce: arrival counter needed while recording: run the call once outside the recording first");
+                WG_HIP_TRY(hipSetDevice(ctx->device));
+                WG_HIP_TRY(hipMalloc((void **)&ctx->flags, 256));
+                WG_HIP_TRY(hipMemsetAsync(ctx->flags, 0, 256, ctx->stream));
+            }
+            return wgk_gemv_small_reduce(ctx, p, (int)op, out_rows, mm.cols, (float *)ws, M, V, ctx->flags, (float *)result->ptr);
         }
-        wgk_mat M = { elem_ptr(m, mm.offset, dtype), mm.stride, mm.stride_mat }, V = { elem_ptr(v, vv.offset, dtype), vv.stride, vv.stride_mat };
-        const int rc = wgk_gemv_small_reduce(ctx, (int)op, out_rows, mm.cols, (float *)ws, M, V, ctx->flags, (float *)result->ptr);
-        if (rc != WG_ERR_UNSUPPORTED) return rc;
     }
     wg_path(ctx, "gemv_reduce.two>");
     wg_buf tmp;

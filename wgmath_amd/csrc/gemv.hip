@@ -20,16 +20,15 @@
 // parity is tolerance-based: the order here is "per-lane sequential, then butterfly", which satisfies the
 // same error bound as both WGSL orders.
 #include "wg_internal.hpp"
-#include "gemm32_plan.hpp"
+#include "gemv_plan.hpp"
 #include "reduce_ops.hpp"
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kMaxRhs = 8; // RHS columns handled per pass over the matrix (m is read once for all of them)
+constexpr int kMaxRhs = kGemvMaxRhs; // RHS columns handled per pass over the matrix (gemv_plan.hpp)
 
 #ifndef GEMV_NT
 #define GEMV_NT 1
@@ -273,9 +272,7 @@ __global__ __launch_bounds__(kThreads) void gemv_t_kernel(GemvArgsT<T, V> a) {
 // float4 beside each (the 8 half-waves of a workgroup read the same addresses: cache hits). 8 columns per workgroup.
 // grid = (column groups of 8, splits, nmats)
 // ------------------------------------------------------------------------------------------------------
-#ifndef WG_GEMVT_U
-#define WG_GEMVT_U 8
-#endif
+// (WG_GEMVT_U, the U of the deep form: gemv_plan.hpp -- the plan names the instance)
 #ifndef WG_GEMVT_ROT
 #define WG_GEMVT_ROT 0 // 1: column c starts its sweep (c * 5) blocks of rows in and wraps around (de-phases the columns' streams)
 #endif
@@ -413,7 +410,7 @@ __global__ __launch_bounds__(kThreads) void gemv_t_cols_kernel(GemvArgsT<T, V> a
 // few-column Gemm kernels run the same products on the matrix cores at 1/4 .. 1/8 utilisation and pay for it in clock).
 // Shape of a workgroup (round 5; before: always 1024 threads x 4 columns per half-wave = 128 columns per trip, which left 2/3 of the chip idle at 11008 outputs):
 // THREADS / 32 half-waves x COLS adjacent columns per trip; the launcher picks the pair that gives every CU a workgroup and, when it can, all of them ONE trip
-// (gemv_t_lds_plan). COLS > 1 shares each LDS piece of the vectors between COLS matrix pieces (8 right-hand sides with COLS = 1 read 8 x the matrix's bytes
+// (gemv_plan.hip t_lds). COLS > 1 shares each LDS piece of the vectors between COLS matrix pieces (8 right-hand sides with COLS = 1 read 8 x the matrix's bytes
 // out of the LDS: 104 of the LDS's 128 bytes per clock at HBM speed).
 // grid = (workgroups, 1, nmats), persistent over the column groups g, g + gridDim.x, ...; dynamic LDS = KC * NRHS * 4 bytes.
 // ------------------------------------------------------------------------------------------------------
@@ -602,12 +599,6 @@ __device__ __forceinline__ float4 gemv_small_rows(const T *mp, uint32_t ldm, con
     }
     return s;
 }
-// rows per workgroup = 4 RL: as few as gives the chip >= 128 workgroups
-static inline int gemv_small_rl(uint32_t rows_out) {
-    static const int forced = [] { const char *e = getenv("WG_GEMV_SMALL_RL"); return e ? atoi(e) : 0; }(); // experiments: 2 / 4 / 8 lanes x float4 of rows per workgroup
-    if (forced == 2 || forced == 4 || forced == 8) return forced;
-    return rows_out >= 4096u ? 8 : (rows_out >= 2048u ? 4 : 2);
-}
 
 template <int RL, typename T, typename V = T>
 __global__ __launch_bounds__(kThreads) void gemv_n_small_kernel(GemvArgsT<T, V> a) {
@@ -675,247 +666,106 @@ __global__ __launch_bounds__(kThreads) void gemv_n_small_reduce_kernel(GemvArgs 
     if (p == 0) result[0] = r[0];
 }
 
-#ifndef GEMV_SMALL
-#define GEMV_SMALL 1
-#endif
-inline uint32_t ceil_div(uint32_t a, uint32_t b) { return a / b + (a % b != 0); }
-
-// blocks along the output, and how finely the contraction must be split to give every CU ~4 workgroups
-#ifndef WG_GEMVT_COLS
-#define WG_GEMVT_COLS 1 // 0: T with one right-hand side on the 4-columns-per-wave kernel as well (the form before round 3)
-#endif
-// T with ONE right-hand side runs on gemv_t_cols_kernel (a half-wave per column): measured over 17 shapes x 2 element types against the
-// 4-columns-per-wave kernel (tools/gemvtr_sweep.py, profiles/r03_evidence.md section 10): f32 -1...-40 % time (4096^2 16.5 -> 10 us, 65536 x 4096
-// 169 -> 162), f16 -5...-45 % (65536 x 4096 95 -> 83 us = 6.5 TB/s) -- except f32 columns exactly 64 KiB apart with k <= 16384 (16384 x 2048 ...
-// x 16384: +5...+13 %; 15360 and 17408 rows are fine, f16 and longer columns at that stride are fine), which stay on the old kernel.
-// gemv_t_cols_kernel with 4 instead of 8 loads in flight per lane (half the registers, twice the half-waves per CU): columns of at most 8 chunks (a chunk: 32 lanes x 16 bytes),
-// and up to 31 chunks when the 8-deep form would end in a partial trip. Measured (tools/gemvtr_sweep.py, f16, us): 1024 x 65536 55 -> 20 (vendor 22), 1280 x 32768 25.4 -> 13.8,
-// 3072 x 65536 74.2 -> 57.0; whole trips of 8 stay (4096 x 65536 f16 75.0 against 79.0, 2048 x 65536 f32 76.5 against 79.5).
-static bool t_cols_u4(uint32_t k_per_split, uint32_t e) {
-    const uint32_t chunks = k_per_split / (32u * e);
-    return chunks <= 8u || (chunks < 32u && chunks % 8u != 0);
-}
-// GemvTr with TWO right-hand sides on the half-wave-per-column kernel's 2-vector form (gemv_t_cols_kernel<.., 4, 2>, round 5): every piece of the matrix meets the same rows
-// of both vectors, no LDS, no barrier. Measured against what took these shapes before (tools/misc_sweep.py with MISC_GEMV_SHAPES, us, before -> after | vendor) -- f16 (the
-// 4-columns-per-wave kernel): 4096^2 14.0 -> 7.7 | 18, 4096 x 11008 24.0 -> 18.5 | 18.5, 11008 x 4096 23.4 -> 18.1 | 19, 8192^2 36.3 -> 25.0 | 22-27, 65536 x 4096 111 -> 88 | 108,
-// 16384^2 104 -> 91 | 98, but few outputs lose (32768 x 1536 28.8 -> 38.7): from 2048 outputs on. f32 (the vectors-in-LDS kernel): only where that kernel's one barrier per chunk
-// shows -- 4096 x 11008 41.8 -> 33.3 | 30, 4096^2 12.8 -> 12.0 -- and worse elsewhere (16384^2 163 -> 188, 11008 x 4096 32.3 -> 34.7): contractions of 2049 .. 8192 rows onto
-// 4096 .. 16384 outputs.
-#ifndef WG_GEMVT_COLS2
-#define WG_GEMVT_COLS2 1
-#endif
-template <typename T>
-static bool uses_t_cols2(bool trans, uint32_t nrhs, uint32_t rows_out, uint32_t k) {
-    if (!WG_GEMVT_COLS2 || !trans || nrhs != 2u) return false;
-    if (sizeof(T) == 2) return rows_out >= 2048u;
-    return k > 2048u && k <= 8192u && rows_out >= 4096u && rows_out <= 16384u;
-}
-template <typename T>
-static bool uses_t_cols(bool trans, uint32_t nrhs, uint32_t k, uint32_t ldm) {
-    if (!WG_GEMVT_COLS || !trans || nrhs != 1) return false;
-    if (sizeof(T) == 4 && ldm % 16384u == 0 && k <= 16384u) return false;
-    return true;
-}
-template <typename T>
-static uint32_t plan_nsplit(int cus, bool trans, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t gz, uint32_t ldm) {
-    const bool cols = uses_t_cols<T>(trans, nrhs, k, ldm) || uses_t_cols2<T>(trans, nrhs, rows_out, k);
-    const uint32_t gx = cols ? ceil_div(rows_out, 8u) : trans ? ceil_div(rows_out, 4u * kWaves) : ceil_div(rows_out, 256u);
-    const uint32_t min_k_per_split = trans ? 2048u : 64u; // T: >= 8 row-steps per lane; N: >= 16 columns per wave
-    const uint64_t blocks_xy = (uint64_t)gx * gz;
-    const uint32_t max_split = k == 0 ? 1u : ceil_div(k, min_k_per_split);
-    // ~4 workgroups per CU (measured at 1 / 2 / 4 per CU: GemvTr 65536 x 4096 5.4 / 6.0 / 6.4 TB/s; Gemv 4096 x 11008 43 / - / 33 us),
-    // except a tall matrix with a short contraction whose row blocks alone give every CU a workgroup: splitting 65536 x 256 four ways
-    // costs 18 us with the combine pass against 10 us unsplit.
-    // N: matrices of 256 MiB and more stream best with 2 workgroups per CU and four times the columns per workgroup (4096 x 32768 f32: 103 -> 83 us,
-    // 16384^2: 167 -> 158, 4096 x 65536: 165.9 -> 162.5; f16 alike), smaller ones with 4 (tools/gemvtr_sweep.py with SWEEP_N=1, r03 evidence section 10)
-    // (round 5: tall matrices from 128 MiB on as well -- 32768 x 1536 f32 39.3 -> 35.9 us, 16384 x 2048 30.4 -> 27.4; not the squarer ones: 8192 x 4096 23.1 -> 27.4, 11008 x 4096 31.2 -> 33.4)
-    const uint64_t n_bytes = (uint64_t)rows_out * k * sizeof(T);
-    const bool big_n = !trans && (n_bytes >= (256ull << 20) || (sizeof(T) == 4 && n_bytes >= (128ull << 20) && rows_out >= 16384u));
-    const uint32_t per_cu = cols ? 2u : trans ? 4u : big_n ? 2u : 4u; // (the half-wave-per-column kernel: 2 / 4 / 8 per CU measured the same within 2 %; fewer splits, smaller combine)
-    uint32_t want = blocks_xy >= (uint64_t)cus * per_cu ? 1u : ceil_div((uint32_t)cus * per_cu, (uint32_t)blocks_xy);
-    if (!trans && blocks_xy >= (uint64_t)cus && k <= 1024u) want = 1u;
-    if (trans && !cols && blocks_xy >= 2ull * (uint64_t)cus) want = 1u; // T with >= 2 workgroups per CU already: 8192 x 8192 47 us unsplit, 57 split in two + combine
-    uint32_t nsplit = want > max_split ? max_split : want;
-    if (nsplit < 1u) nsplit = 1u;
-    if (nsplit > 65535u) nsplit = 65535u;
-    if (nrhs > 65535u) nsplit = 1u; // the combine pass puts the right-hand sides on grid.y; that many columns fill the chip unsplit
-    return nsplit;
-}
-// wgk_gemv runs launch-bound Gemvs as ONE kernel without partials (gemv_n_small_kernel); the fused Gemv+Reduce must pick exactly those
-static bool uses_small_kernel(int cus, bool trans, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nsplit) {
-    return GEMV_SMALL && !trans && nsplit > 1 && (uint64_t)rows_out * k <= (4ull << 20) && rows_out >= 128u && nrhs <= 65535u;
-}
-
 } // namespace
 
-// (V != T: the mixed call -- the plan below is made with the MATRIX's element type, so it is the plan of gemv_launch<T> for the same shape, views and context)
+// ------------------------------------------------------------------------------------------------------
+// The launchers: fill a query, ask gemv_plan (gemv_plan.hip: every choice of kernel, tile, cut, grid and workspace, with the measurements behind it), do what the
+// plan says and log its tags.
+// ------------------------------------------------------------------------------------------------------
+wg_gemv_query wgk_gemv_query(const wg_ctx *ctx, bool trans, wg_dtype m_dtype, wg_dtype v_dtype, bool gemm16, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats,
+                             uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v) {
+    wg_gemv_query q = {};
+    q.trans = trans; q.rows_out = rows_out; q.k = k; q.nrhs = nrhs; q.nmats = nmats;
+    q.m_elem = (uint32_t)wg_dtype_size(m_dtype); q.v_elem = (uint32_t)wg_dtype_size(v_dtype);
+    q.bf16 = m_dtype == WG_BF16; q.gemm16 = gemm16;
+    q.ldm = m.ld; q.ldv = v.ld; q.ldo = out_ld;
+    q.m_batch = m.batch; q.v_batch = v.batch; q.o_batch = out_batch;
+    q.m_addr16 = (uint32_t)((uintptr_t)m.ptr % 16); q.v_addr16 = (uint32_t)((uintptr_t)v.ptr % 16);
+    q.cus = (uint32_t)wg_ctx_cus(ctx);
+    q.gemvt_lds = ctx->tuning[WG_TUNE_GEMVT_LDS];
+    return q;
+}
+
+// The plan's own kernels: small, n, t, tcols, and the combine pass of a cut. (V != T: the mixed call)
 template <typename T, typename V = T>
-static int gemv_launch(wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, V *out, uint32_t out_ld, uint64_t out_batch,
+static int gemv_launch(wg_ctx *ctx, const wg_gemv_plan &p, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, V *out, uint32_t out_ld, uint64_t out_batch,
                        wgk_mat m, wgk_mat v) {
-    const int cus = wg_ctx_cus(ctx);
-    const uint32_t rhs_groups = ceil_div(nrhs, kMaxRhs);
-    const uint64_t gz64 = (uint64_t)nmats * rhs_groups;
-    if (gz64 > 65535) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemv: nmats * ceil(nrhs/8) = %llu exceeds 65535", (unsigned long long)gz64);
-    const uint32_t gz = (uint32_t)gz64;
-
-    const bool t_cols = uses_t_cols<T>(trans, nrhs, k, m.ld) || uses_t_cols2<T>(trans, nrhs, rows_out, k);
-    const uint32_t gx = t_cols ? ceil_div(rows_out, 8u) : trans ? ceil_div(rows_out, 4u * kWaves) : ceil_div(rows_out, 256u);
-    uint32_t nsplit = plan_nsplit<T>(cus, trans, rows_out, k, nrhs, gz, m.ld);
-    uint32_t k_per_split = k == 0 ? 4u : ceil_div(ceil_div(k, nsplit), 4u) * 4u; // vec4 granularity
-    nsplit = k == 0 ? 1u : ceil_div(k, k_per_split);
-
     GemvArgsT<T, V> a;
     a.m = (const T *)m.ptr; a.ldm = m.ld; a.m_batch = m.batch;
     a.v = (const V *)v.ptr; a.ldv = v.ld; a.v_batch = v.batch;
-    a.rows_out = rows_out; a.k = k; a.nrhs = nrhs; a.k_per_split = k_per_split;
+    a.rows_out = rows_out; a.k = k; a.nrhs = nrhs; a.k_per_split = p.k_per_split;
     a.out = out;
     a.part = nullptr;
-    // launch-bound sizes: one kernel without partials beats split + combine (1024 x 1024: 12.6 -> ~9 us per eager dispatch); it needs no workspace
-    // (so that a recording on a fresh context does not ask for one)
-    const bool small = uses_small_kernel(cus, trans, rows_out, k, nrhs, nsplit);
-    if (nsplit > 1 && !small) { // f32 partial sums whatever the element type
-        size_t bytes = (size_t)nmats * nsplit * nrhs * rows_out * sizeof(float);
+    if (p.nsplit > 1) { // f32 partial sums whatever the element type
         void *ws = nullptr;
-        if (int rc = wg_ctx_workspace(ctx, bytes, &ws)) return rc;
+        if (int rc = wg_ctx_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
         a.part = (float *)ws;
         a.ld_dst = rows_out;
         a.dst_split = (uint64_t)nrhs * rows_out;
-        a.dst_batch = (uint64_t)nsplit * nrhs * rows_out;
+        a.dst_batch = (uint64_t)p.nsplit * nrhs * rows_out;
     } else {
         a.ld_dst = out_ld;
         a.dst_split = 0;
         a.dst_batch = out_batch;
     }
-
-    if (small) {
-        const int rl = gemv_small_rl(rows_out);
-        wg_path(ctx, "gemv.small/rl=%d", rl);
-        const dim3 sg(ceil_div(rows_out, 4u * (uint32_t)rl), nrhs, nmats);
-        if (rl == 8) hipLaunchKernelGGL((gemv_n_small_kernel<8, T, V>), sg, dim3(kThreads), 0, ctx->stream, a);
-        else if (rl == 4) hipLaunchKernelGGL((gemv_n_small_kernel<4, T, V>), sg, dim3(kThreads), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((gemv_n_small_kernel<2, T, V>), sg, dim3(kThreads), 0, ctx->stream, a);
-        WG_HIP_TRY(hipGetLastError());
-        return WG_OK;
-    }
-    const dim3 grid(gx, nsplit, gz), block(kThreads);
-    // kMaxRhs RHS columns per group (grid.z); the kernel template is the per-pass register tile: the smallest of 1, 2, 4, 8 that
-    // holds min(nrhs, 8) columns (a group of 3 uses tile 4, of 5..7 tile 8)
-    const uint32_t per_group = nrhs < (uint32_t)kMaxRhs ? nrhs : (uint32_t)kMaxRhs;
-    const int tile = per_group > 4 ? 8 : (per_group > 2 ? 4 : (int)per_group);
-    if (t_cols) {
-        // f16: 16-byte loads (8 rows per lane) where every column, split and batch keeps them aligned; 8-byte loads (the view contract) otherwise
-        // (v16: elements of the vectors' type per 16 bytes -- f32 vectors beside a 16-bit matrix are read as two 16-byte loads per 8 rows)
-        bool wide = false;
-        constexpr uint32_t v16 = 16u / sizeof(V);
-        if constexpr (sizeof(T) == 2)
-            wide = (uintptr_t)a.m % 16 == 0 && (uintptr_t)a.v % 16 == 0 && a.ldm % 8 == 0 && a.k_per_split % 8 == 0 && (nmats == 1 || (a.m_batch % 8 == 0 && a.v_batch % v16 == 0)) &&
-                   (nrhs == 1 || a.ldv % v16 == 0);
-        // (the tag names the instance the branches below launch: elements per load, loads in flight, right-hand sides)
-        const int te = wide ? 8 : 4, tu = nrhs == 2 || t_cols_u4(a.k_per_split, (uint32_t)te) ? 4 : WG_GEMVT_U;
-        wg_path(ctx, "gemv.tcols/e=%d,u=%d,v=%u,ns=%u", te, tu, nrhs, nsplit);
-        if (nrhs == 2) { // (uses_t_cols2)
+    const GemvTags tags = gemv_tags(p);
+    wg_path(ctx, "%s", tags.tag[0]);
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
+    // the instance of each ladder is named by the plan's fields, the ones its tag prints
+    if (p.leaf == WG_GEMV_SMALL) {
+        if (p.rl == 8) hipLaunchKernelGGL((gemv_n_small_kernel<8, T, V>), grid, block, 0, ctx->stream, a);
+        else if (p.rl == 4) hipLaunchKernelGGL((gemv_n_small_kernel<4, T, V>), grid, block, 0, ctx->stream, a);
+        else hipLaunchKernelGGL((gemv_n_small_kernel<2, T, V>), grid, block, 0, ctx->stream, a);
+    } else if (p.leaf == WG_GEMV_TCOLS) {
+#define WG_GEMV_TCOLS_I(E, U, NR) hipLaunchKernelGGL((gemv_t_cols_kernel<T, E, U, NR, V>), grid, block, 0, ctx->stream, a)
+        if (p.v == 2) {
             if constexpr (sizeof(T) == 2) {
-                if (wide) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, 4, 2, V>), grid, block, 0, ctx->stream, a);
-                else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 2, V>), grid, block, 0, ctx->stream, a);
-            } else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 2, V>), grid, block, 0, ctx->stream, a);
+                if (p.e == 8) WG_GEMV_TCOLS_I(8, 4, 2);
+                else WG_GEMV_TCOLS_I(4, 4, 2);
+            } else WG_GEMV_TCOLS_I(4, 4, 2);
         } else if constexpr (sizeof(T) == 2) {
-            if (wide && t_cols_u4(a.k_per_split, 8u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, 4, 1, V>), grid, block, 0, ctx->stream, a);
-            else if (wide) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 8, WG_GEMVT_U, 1, V>), grid, block, 0, ctx->stream, a);
-            else if (t_cols_u4(a.k_per_split, 4u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 1, V>), grid, block, 0, ctx->stream, a);
-            else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, WG_GEMVT_U, 1, V>), grid, block, 0, ctx->stream, a);
-        } else if (t_cols_u4(a.k_per_split, 4u)) hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, 4, 1, V>), grid, block, 0, ctx->stream, a);
-        else hipLaunchKernelGGL((gemv_t_cols_kernel<T, 4, WG_GEMVT_U, 1, V>), grid, block, 0, ctx->stream, a);
-    }
-    else if (trans) {
-        wg_path(ctx, "gemv.t/t=%d,ns=%u", tile, nsplit);
-        if (tile == 1) hipLaunchKernelGGL((gemv_t_kernel<1, T, V>), grid, block, 0, ctx->stream, a);
-        else if (tile == 2) hipLaunchKernelGGL((gemv_t_kernel<2, T, V>), grid, block, 0, ctx->stream, a);
-        else if (tile == 4) hipLaunchKernelGGL((gemv_t_kernel<4, T, V>), grid, block, 0, ctx->stream, a);
+            if (p.e == 8 && p.u == 4) WG_GEMV_TCOLS_I(8, 4, 1);
+            else if (p.e == 8) WG_GEMV_TCOLS_I(8, WG_GEMVT_U, 1);
+            else if (p.u == 4) WG_GEMV_TCOLS_I(4, 4, 1);
+            else WG_GEMV_TCOLS_I(4, WG_GEMVT_U, 1);
+        } else if (p.u == 4) WG_GEMV_TCOLS_I(4, 4, 1);
+        else WG_GEMV_TCOLS_I(4, WG_GEMVT_U, 1);
+#undef WG_GEMV_TCOLS_I
+    } else if (p.leaf == WG_GEMV_T) {
+        if (p.rhs_tile == 1) hipLaunchKernelGGL((gemv_t_kernel<1, T, V>), grid, block, 0, ctx->stream, a);
+        else if (p.rhs_tile == 2) hipLaunchKernelGGL((gemv_t_kernel<2, T, V>), grid, block, 0, ctx->stream, a);
+        else if (p.rhs_tile == 4) hipLaunchKernelGGL((gemv_t_kernel<4, T, V>), grid, block, 0, ctx->stream, a);
         else hipLaunchKernelGGL((gemv_t_kernel<8, T, V>), grid, block, 0, ctx->stream, a);
     } else {
-        wg_path(ctx, "gemv.n/t=%d,ns=%u", tile, nsplit);
         typedef typename std::conditional<std::is_same<T, V>::value, T, MixedElems<T, V>>::type NE; // (gemv_n_kernel's one argument for the element types)
 #define WG_GEMV_N(NR) hipLaunchKernelGGL((gemv_n_kernel<NR, NE>), grid, block, 0, ctx->stream, a)
-        if (tile == 1) WG_GEMV_N(1);
-        else if (tile == 2) WG_GEMV_N(2);
-        else if (tile == 4) WG_GEMV_N(4);
+        if (p.rhs_tile == 1) WG_GEMV_N(1);
+        else if (p.rhs_tile == 2) WG_GEMV_N(2);
+        else if (p.rhs_tile == 4) WG_GEMV_N(4);
         else WG_GEMV_N(8);
 #undef WG_GEMV_N
     }
     WG_HIP_TRY(hipGetLastError());
-    if (nsplit > 1) {
-        wg_path(ctx, "gemv.combine/ns=%u", nsplit);
-        hipLaunchKernelGGL(gemv_combine_kernel<V>, dim3(ceil_div(rows_out / 4u, 4u), nrhs, nmats), block, 0, ctx->stream, a.part, nsplit, rows_out, nrhs, out,
-                           out_ld, out_batch);
+    if (p.nsplit > 1) {
+        wg_path(ctx, "%s", tags.tag[1]);
+        hipLaunchKernelGGL(gemv_combine_kernel<V>, dim3(p.combine_grid[0], p.combine_grid[1], p.combine_grid[2]), block, 0, ctx->stream, a.part, p.nsplit, rows_out, nrhs,
+                           out, out_ld, out_batch);
         WG_HIP_TRY(hipGetLastError());
     }
     return WG_OK;
 }
 
-// 3 .. 8 right-hand sides on a matrix that is not launch-bound: the GEMV kernels re-read the vectors once per matrix piece (GemvTr) or give every
-// right-hand side its own accumulators (f16 Gemv), and fall well behind one pass on the matrix cores -- measured against both and against the
-// vendor's skinny GEMMs (tools/misc_sweep.py, profiles/r03_evidence.md section 12): f16 GemvTr 65536 x 4096 x 8 373 -> 135 us, f32 GemvTr 4096^2 x 8
-// 33 -> 18 us, f16 Gemv 65536 x 4096 x 8 138 -> 123 us. Kept on the GEMV kernels: 2 right-hand sides, matrices under 48 MiB (one launch instead
-// of several), f32 Gemv (the N kernel streams 8 right-hand sides at 6.2 TB/s), and f32 GemvTr with >= 8 outputs per contracted row (212 vs 279 us).
-static bool few_rhs_as_gemm(bool trans, bool f16, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t es) {
-    const uint64_t bytes = (uint64_t)rows_out * k * es;
-    if (nrhs < 3u || bytes < ((nrhs >= 7u ? 16ull : 48ull) << 20)) return false; // (7-8 right-hand sides pay from 16 MiB: 4096^2 f16 x 8 26 -> 19 us)
-    if (trans) return f16 || (uint64_t)rows_out < 8ull * k;
-    // f32 Gemv: since the few-column Gemm kernel multiplies N <= 16 on 16-wide MFMAs (round 5) it is ahead of the 8-accumulator N kernel on everything but a few
-    // rows with a long contraction (11008 x 4096 x 4: 36.4 -> 33.2 us, 65536 x 4096 x 8: 187 -> 176, 8192^2 x 3: 47.7 -> 42.9; 4096 x 65536 x 8: 173 stays, Gemm 180)
-    // (With the non-temporal hint on its streamed pieces -- gemm_f32_skinny.hip tr_dma_streamed, round 5 -- the Gemm form of 4096 x 65536 x 8 takes 160 us in a replayed
-    // command buffer and 175 +- 14 us, at 1.79 GHz, as eager dispatches in bench.py, against the N kernel's steady 173 at 2.39 GHz: it stays on the N kernel.)
-    return f16 || (uint64_t)k < 8ull * rows_out;
-}
-
-#ifndef WG_GEMVT_LDS
-#define WG_GEMVT_LDS 1
-#endif
-// GemvTr with 2 .. 8 right-hand sides on gemv_t_lds_kernel: shape of the workgroups, chunk of k in the LDS, grid.
-struct TLdsPlan {
-    int cols, threads;   // columns per half-wave, threads per workgroup
-    uint32_t kc, grid;   // contracted rows per LDS chunk (== k: one chunk), workgroups
-    size_t lds;
-};
-static TLdsPlan gemv_t_lds_plan(uint32_t cus, uint32_t rows_out, uint32_t k, uint32_t tile) {
-    TLdsPlan pl;
-    // the vectors whole when k x tile floats fit 128 KiB (then they are staged once per workgroup), else chunks of 64 KiB (two workgroups per CU)
-    const uint32_t whole = (128u << 10) / (tile * 4u), chunk = (64u << 10) / (tile * 4u);
-    pl.kc = k <= whole ? k : chunk;
-    pl.lds = (size_t)pl.kc * tile * sizeof(float);
-    static const int shapes[5][2] = { { 4, 1024 }, { 2, 1024 }, { 1, 1024 }, { 1, 512 }, { 1, 256 } }; // 128, 64, 32, 16, 8 columns per trip
-    double best = 1e30;
-    pl.cols = 1; pl.threads = 256; pl.grid = 1;
-    for (const auto &sh : shapes) {
-        const uint32_t per_wg = (uint32_t)sh[0] * (uint32_t)sh[1] / 32u;
-        const uint32_t groups = ceil_div(rows_out, per_wg);
-        uint32_t per_cu = (uint32_t)((160u << 10) / (pl.lds ? pl.lds : 1));
-        if (per_cu > 2048u / (uint32_t)sh[1]) per_cu = 2048u / (uint32_t)sh[1];
-        if (per_cu < 1u) per_cu = 1u;
-        const uint32_t slots = cus * per_cu, grid = groups < slots ? groups : slots;
-        const uint32_t trips = ceil_div(groups, grid);
-        // relative time: work per workgroup slot in column-trips, against an even share; a grid that leaves CUs without a workgroup pays for them;
-        // narrower shapes pay a little for re-reading the vectors from the LDS per column (COLS = 1) and for staging them per workgroup
-        double f = (double)trips * grid / (double)groups;
-        if (groups < cus) f *= (double)cus / groups;
-        // (staging: tile floats of the vectors per contracted row against per_wg floats of the matrix, from the L2; once per workgroup when k is one chunk)
-        f *= 1.0 + 0.02 * (4 - sh[0]) + 0.5 * (double)tile / per_wg * (k > pl.kc ? 1.0 : 1.0 / trips);
-        if (f < best) { best = f; pl.cols = sh[0]; pl.threads = sh[1]; pl.grid = grid; }
-    }
-    return pl;
-}
+// WG_GEMV_TLDS: workgroup shape, chunk of k in the LDS and grid are the plan's
 template <typename T>
-static int gemv_t_lds_launch(wg_ctx *ctx, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, T *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v) {
+static int gemv_t_lds_launch(wg_ctx *ctx, const wg_gemv_plan &p, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, T *out, uint32_t out_ld, uint64_t out_batch,
+                             wgk_mat m, wgk_mat v) {
     GemvArgsT<T> a;
     a.m = (const T *)m.ptr; a.ldm = m.ld; a.m_batch = m.batch;
     a.v = (const T *)v.ptr; a.ldv = v.ld; a.v_batch = v.batch;
     a.rows_out = rows_out; a.k = k; a.nrhs = nrhs; a.k_per_split = k;
     a.out = out; a.part = nullptr; a.ld_dst = out_ld; a.dst_split = 0; a.dst_batch = out_batch;
-    const int tile = nrhs > 4 ? 8 : (nrhs > 2 ? 4 : 2);
-    const uint32_t cus = (uint32_t)wg_ctx_cus(ctx);
-    const TLdsPlan pl = gemv_t_lds_plan(cus, rows_out, k, (uint32_t)tile);
-    const dim3 grid(pl.grid, 1, nmats);
-    wg_path(ctx, "gemv.tlds/nr=%d,c=%d,th=%d", tile, pl.cols, pl.threads);
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    wg_path(ctx, "%s", gemv_tags(p).tag[0]);
     // hipFuncAttributeMaxDynamicSharedMemorySize once per context (= per device and stream) and instantiation: bit = 5 * tile index + shape index
 #define WG_T_LDS(NR, COLS, THREADS, SHAPE)                                                                                                     \
     do {                                                                                                                                       \
@@ -924,111 +774,82 @@ static int gemv_t_lds_launch(wg_ctx *ctx, uint32_t rows_out, uint32_t k, uint32_
             WG_HIP_TRY(hipFuncSetAttribute((const void *)gemv_t_lds_kernel<NR, T, COLS, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
             ctx->lds_attr_bits |= bit;                                                                                                         \
         }                                                                                                                                      \
-        hipLaunchKernelGGL((gemv_t_lds_kernel<NR, T, COLS, THREADS>), grid, dim3(THREADS), pl.lds, ctx->stream, a, pl.kc);                     \
+        hipLaunchKernelGGL((gemv_t_lds_kernel<NR, T, COLS, THREADS>), grid, dim3(THREADS), p.lds_bytes, ctx->stream, a, p.lds_kc);             \
     } while (0)
 #define WG_T_LDS_SHAPES(NR)                                                            \
     do {                                                                               \
-        if (pl.cols == 4) WG_T_LDS(NR, 4, 1024, 0);                                    \
-        else if (pl.cols == 2) WG_T_LDS(NR, 2, 1024, 1);                               \
-        else if (pl.threads == 1024) WG_T_LDS(NR, 1, 1024, 2);                         \
-        else if (pl.threads == 512) WG_T_LDS(NR, 1, 512, 3);                           \
+        if (p.lds_cols == 4) WG_T_LDS(NR, 4, 1024, 0);                                 \
+        else if (p.lds_cols == 2) WG_T_LDS(NR, 2, 1024, 1);                            \
+        else if (p.lds_threads == 1024) WG_T_LDS(NR, 1, 1024, 2);                      \
+        else if (p.lds_threads == 512) WG_T_LDS(NR, 1, 512, 3);                        \
         else WG_T_LDS(NR, 1, 256, 4);                                                  \
     } while (0)
-    if (tile == 8) WG_T_LDS_SHAPES(8); else if (tile == 4) WG_T_LDS_SHAPES(4); else WG_T_LDS_SHAPES(2);
+    if (p.rhs_tile == 8) WG_T_LDS_SHAPES(8); else if (p.rhs_tile == 4) WG_T_LDS_SHAPES(4); else WG_T_LDS_SHAPES(2);
 #undef WG_T_LDS_SHAPES
 #undef WG_T_LDS
     WG_HIP_TRY(hipGetLastError());
     return WG_OK;
 }
-// Where it runs (f32 only: f16 gains nothing over the f16 Gemm kernels, 120 vs 111 us at 4096 x 65536 x 8), measured with tools/misc_sweep.py
-// (profiles/r05_evidence.md section 5):
-//   * from 128 outputs per CU on, the vectors whole in the LDS: 4096 x 65536 x 8 178 us against 212 on the
-//     4-columns-per-wave kernel and 279 on the few-column Gemm kernel (vendor 178);
-//   * TWO right-hand sides from 8 outputs per CU on (the narrow workgroup shapes of round 5): 4096^2 x 2 18.2 -> 12.8 us (vendor 18.9);
-//   * NOT 3 .. 8 right-hand sides on fewer outputs: every workgroup shape loses to the matrix-core path there (4096 x 11008 x 4: 55 us on 344 workgroups
-//     of 32 columns, 86 with twice the loads in flight, against 40 on the few-column Gemm kernel; 4096^2 x 8 26.5 against 18.1) -- a column is 16 KiB,
-//     each half-wave's whole life is a few dependent round trips behind the staging of the vectors.
-static bool uses_t_lds(const wg_ctx *ctx, bool trans, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, uint32_t es) {
-    if (!WG_GEMVT_LDS || !trans || es != 4u || nrhs < 2u || nrhs > 8u || nmats > 65535u) return false;
-    if (!ctx->tuning[WG_TUNE_GEMVT_LDS] && uses_t_cols2<float>(trans, nrhs, rows_out, k)) return false; // (two right-hand sides on the column kernel's 2-vector form)
-    const uint32_t forced = (uint32_t)ctx->tuning[WG_TUNE_GEMVT_LDS], min_cols = forced ? forced : 128u; // (forced: tests, experiments -- wg_ctx_set_tuning)
-    const uint32_t cus = (uint32_t)wg_ctx_cus(ctx);
-    const uint32_t tile = nrhs > 4u ? 8u : (nrhs > 2u ? 4u : 2u);
-    if (rows_out % 4u || k % 4u || k < 128u) return false;
-    const bool whole = (uint64_t)k * tile * 4u <= (128u << 10);                       // one chunk: staged once per workgroup
-    const bool chunks_ok = whole || (uint64_t)k * tile * 4u <= 4ull * (64u << 10);     // at most 4 chunks (two barriers per chunk and trip)
-    if ((uint64_t)rows_out >= (uint64_t)min_cols * cus) return forced ? chunks_ok : whole;
-    return nrhs == 2u && whole && (uint64_t)rows_out >= 8ull * cus;
+
+// a refusal of the plan, behind the tags the launcher logs in front of what it would have launched (a refused hand-off: the wrapper alone)
+static int gemv_refused(wg_ctx *ctx, const wg_gemv_query &q, const wg_gemv_plan &p) {
+    wg_path(ctx, "gemv>");
+    if (p.gemm32.leaf != WG_GEMM32_UNSUPPORTED) wg_path(ctx, "%s", gemv_elem_tag(q));
+    return wg_set_error(p.status, "%s", p.message);
 }
 
-// (Round 5 also carried the half-wave-per-column shape of gemv_t_cols_kernel over to 2 .. 8 right-hand sides -- four adjacent columns per half-wave, the
-// vectors re-read through the L1 -- and measured it slower than every path above on all eight sweep cases (4096^2 x 4: 35.8 us against 18.3 on the few-column
-// Gemm kernel; 4096 x 11008 x 4: 47 against 39): the re-reads cost the L1 as much as the matrix itself. Removed; profiles/r05_evidence.md section 5.)
 int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats,
              void *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v) {
-    if (rows_out == 0 || nrhs == 0 || nmats == 0) return WG_OK;
+    const wg_gemv_query q = wgk_gemv_query(ctx, trans, dtype, dtype, dtype != WG_F32, rows_out, k, nrhs, nmats, out_ld, out_batch, m, v);
+    const wg_gemv_plan p = gemv_plan(q);
+    switch (p.leaf) {
+    case WG_GEMV_NOTHING: return WG_OK;
+    case WG_GEMV_UNSUPPORTED: return gemv_refused(ctx, q, p);
+    default: break;
+    }
     wg_path(ctx, "gemv>");
-    if (uses_t_lds(ctx, trans, rows_out, k, nrhs, nmats, (uint32_t)wg_dtype_size(dtype))) {
-        return gemv_t_lds_launch<float>(ctx, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
+    switch (p.leaf) {
+    case WG_GEMV_TLDS: return gemv_t_lds_launch<float>(ctx, p, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
+    case WG_GEMV_AS_GEMM16: // (that launcher plans the call: gemm16_plan.hip)
+        if (dtype == WG_F16) return wgk_gemm_f16(ctx, trans, rows_out, nrhs, k, nmats, (__half *)out, out_ld, out_batch, m, v, 1.f, 0.f);
+        return wgk_gemm_bf16(ctx, trans, rows_out, nrhs, k, nmats, (wg_bf16 *)out, out_ld, out_batch, m, v, 1.f, 0.f);
+    case WG_GEMV_AS_GEMM32: return wgk_gemm_f32_skinny(ctx, p.gemm32, trans, rows_out, nrhs, k, nmats, (float *)out, out_ld, out_batch, m, v, 1.f, 0.f);
+    default: break;
     }
-    if (dtype == WG_F16) {
-        // f16 (extension; the reference kernel is f32, gemv.wgsl:9-14): the same HBM-bound kernels on f16 elements (8-byte loads of 4 rows,
-        // f32 accumulation in the same order, one rounding at the store; split partials stay f32). More than 8 right-hand sides are a
-        // Gemm with few columns: the f16 Gemm kernels take any column count (one pass over the matrix on the matrix cores).
-        if (nrhs > (uint32_t)kMaxRhs || few_rhs_as_gemm(trans, true, rows_out, k, nrhs, 2u))
-            return wgk_gemm_f16(ctx, trans, rows_out, nrhs, k, nmats, (__half *)out, out_ld, out_batch, m, v, 1.f, 0.f);
-        wg_path(ctx, "f16.gemv");
-        return gemv_launch<_Float16>(ctx, trans, rows_out, k, nrhs, nmats, (_Float16 *)out, out_ld, out_batch, m, v);
-    }
-    if (dtype == WG_BF16) { // (extension, as f16: the same kernels and the same dispatch on bfloat16 elements)
-        if (nrhs > (uint32_t)kMaxRhs || few_rhs_as_gemm(trans, true, rows_out, k, nrhs, 2u))
-            return wgk_gemm_bf16(ctx, trans, rows_out, nrhs, k, nmats, (wg_bf16 *)out, out_ld, out_batch, m, v, 1.f, 0.f);
-        wg_path(ctx, "bf16.gemv");
-        return gemv_launch<wg_bf16>(ctx, trans, rows_out, k, nrhs, nmats, (wg_bf16 *)out, out_ld, out_batch, m, v);
-    }
-    // 9 .. 64 right-hand sides are a Gemm with few columns: one pass over the matrix on the matrix cores (gemm_f32_skinny.hip) instead of
-    // one GEMV pass per 8 columns. (The 32-bit DMA offsets of that kernel must suffice for both operands, in both variants.)
-    if ((nrhs > (uint32_t)kMaxRhs || few_rhs_as_gemm(trans, false, rows_out, k, nrhs, 4u)) && nrhs <= 64u && rows_out >= 512u && k >= 128u &&
-        (uint64_t)m.ld * 32u * 4u < (1ull << 31) && (uint64_t)v.ld * 64u * 4u < (1ull << 31)) {
-        const wg_gemm32_plan p = gemm32_skinny_plan(rows_out, nrhs, k, nmats, (uint32_t)wg_ctx_cus(ctx)); // its K cut
-        if (p.leaf == WG_GEMM32_UNSUPPORTED) return wg_set_error(p.status, "%s", p.message);
-        return wgk_gemm_f32_skinny(ctx, p, trans, rows_out, nrhs, k, nmats, (float *)out, out_ld, out_batch, m, v, 1.f, 0.f);
-    }
-    wg_path(ctx, "f32.gemv");
-    return gemv_launch<float>(ctx, trans, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
+    wg_path(ctx, "%s", gemv_elem_tag(q));
+    if (dtype == WG_F16) return gemv_launch<_Float16>(ctx, p, rows_out, k, nrhs, nmats, (_Float16 *)out, out_ld, out_batch, m, v);
+    if (dtype == WG_BF16) return gemv_launch<wg_bf16>(ctx, p, rows_out, k, nrhs, nmats, (wg_bf16 *)out, out_ld, out_batch, m, v);
+    return gemv_launch<float>(ctx, p, rows_out, k, nrhs, nmats, (float *)out, out_ld, out_batch, m, v);
 }
 
-// wg_gemv_mixed: a 16-bit matrix, f32 vectors and result. Always the Gemv kernels (the Gemm kernels of the 16-bit wgk_gemv would round v to 16 bits): more than
-// 8 right-hand sides run as groups of 8 in grid.z, one pass over the matrix per group.
+// wg_gemv_mixed: a 16-bit matrix, f32 vectors and result. Always the Gemv kernels (the plan hands a mixed query to no Gemm kernel).
 int wgk_gemv_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
                    wgk_mat m, wgk_mat v) {
-    if (rows_out == 0 || nrhs == 0 || nmats == 0) return WG_OK;
+    const wg_gemv_query q = wgk_gemv_query(ctx, trans, m_dtype, WG_F32, false, rows_out, k, nrhs, nmats, out_ld, out_batch, m, v);
+    const wg_gemv_plan p = gemv_plan(q);
+    if (p.leaf == WG_GEMV_NOTHING) return WG_OK;
+    if (p.leaf == WG_GEMV_UNSUPPORTED) return gemv_refused(ctx, q, p);
     wg_path(ctx, "gemv>");
-    if (m_dtype == WG_F16) {
-        wg_path(ctx, "f16w.gemv");
-        return gemv_launch<_Float16, float>(ctx, trans, rows_out, k, nrhs, nmats, out, out_ld, out_batch, m, v);
-    }
-    wg_path(ctx, "bf16w.gemv");
-    return gemv_launch<wg_bf16, float>(ctx, trans, rows_out, k, nrhs, nmats, out, out_ld, out_batch, m, v);
+    wg_path(ctx, "%s", gemv_elem_tag(q));
+    if (m_dtype == WG_F16) return gemv_launch<_Float16, float>(ctx, p, rows_out, k, nrhs, nmats, out, out_ld, out_batch, m, v);
+    return gemv_launch<wg_bf16, float>(ctx, p, rows_out, k, nrhs, nmats, out, out_ld, out_batch, m, v);
 }
 
-// One launch for result = reduce(op, m v) when the Gemv is launch-bound (the single-kernel shape family of wgk_gemv); WG_ERR_UNSUPPORTED
-// tells the caller to run Gemv and Reduce as two launches. `y` is a scratch vector of rows_out floats, `counter` a zeroed device word.
-int wgk_gemv_small_reduce(wg_ctx *ctx, int op, uint32_t rows_out, uint32_t k, float *y, wgk_mat m, wgk_mat v, unsigned *counter, float *result) {
-    const int cus = wg_ctx_cus(ctx);
-    if (k < 4u || !uses_small_kernel(cus, false, rows_out, k, 1, plan_nsplit<float>(cus, false, rows_out, k, 1, 1, m.ld))) return WG_ERR_UNSUPPORTED;
+// One launch for result = reduce(op, m v) when the Gemv is launch-bound: `p` is the plan of that Gemv (one matrix, one f32 vector) and its leaf is WG_GEMV_SMALL --
+// the caller (api.hip wg_gemv_reduce) runs every other call as Gemv and Reduce, two launches. `y` is a scratch vector of rows_out floats, `counter` a zeroed device word.
+int wgk_gemv_small_reduce(wg_ctx *ctx, const wg_gemv_plan &p, int op, uint32_t rows_out, uint32_t k, float *y, wgk_mat m, wgk_mat v, unsigned *counter, float *result) {
+    if (p.leaf != WG_GEMV_SMALL) return wg_set_error(WG_ERR_INVALID_ARG, "gemv_reduce: not a plan of the single-kernel Gemv");
     GemvArgs a;
     a.m = (const float *)m.ptr; a.ldm = m.ld; a.m_batch = 0;
     a.v = (const float *)v.ptr; a.ldv = v.ld; a.v_batch = 0;
     a.rows_out = rows_out; a.k = k; a.nrhs = 1; a.k_per_split = k;
     a.out = y; a.part = nullptr; a.ld_dst = rows_out; a.dst_split = 0; a.dst_batch = 0;
-    const int rl = gemv_small_rl(rows_out);
-    const dim3 grid(ceil_div(rows_out, 4u * (uint32_t)rl)), block(kThreads);
-    wg_path(ctx, "gemv.small_reduce/rl=%d", rl);
+    const dim3 grid(p.grid[0]), block(p.block);
+    wg_path(ctx, "gemv.small_reduce/rl=%u", p.rl);
 #define WG_SMALL_REDUCE(OP)                                                                                                          \
     do {                                                                                                                             \
-        if (rl == 8) hipLaunchKernelGGL((gemv_n_small_reduce_kernel<OP, 8>), grid, block, 0, ctx->stream, a, counter, result);        \
-        else if (rl == 4) hipLaunchKernelGGL((gemv_n_small_reduce_kernel<OP, 4>), grid, block, 0, ctx->stream, a, counter, result);   \
+        if (p.rl == 8) hipLaunchKernelGGL((gemv_n_small_reduce_kernel<OP, 8>), grid, block, 0, ctx->stream, a, counter, result);      \
+        else if (p.rl == 4) hipLaunchKernelGGL((gemv_n_small_reduce_kernel<OP, 4>), grid, block, 0, ctx->stream, a, counter, result); \
         else hipLaunchKernelGGL((gemv_n_small_reduce_kernel<OP, 2>), grid, block, 0, ctx->stream, a, counter, result);               \
     } while (0)
     switch (op) {

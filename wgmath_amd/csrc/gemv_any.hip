@@ -14,12 +14,10 @@
 // A small second kernel sums the partials in a fixed order. Order of the sums: per lane in sequence, then across lanes / waves / splits -- the
 // tolerance contract of gemv.hip, not its bits.
 #include "wg_internal.hpp"
+#include "gemv_plan.hpp"
 
 #ifndef WG_ANY_NU
 #define WG_ANY_NU 8 // N: columns in flight per lane
-#endif
-#ifndef WG_ANY_PER_CU
-#define WG_ANY_PER_CU 0 // workgroups per CU the splits aim at; 0: 2, and 4 for N on matrices of 1 GiB and more (cliff sweep A/B, profiles/r06_gemv_any_ab.txt)
 #endif
 
 namespace {
@@ -208,50 +206,41 @@ __global__ __launch_bounds__(kThreads) void gemv_any_combine_kernel(AnyArgs a, u
     reinterpret_cast<T *>(a.out)[z * a.o_batch + (uint64_t)y * a.ldo + i] = (T)s;
 }
 
-template <typename T, typename V = T> // (V != T: wg_gemv_mixed -- splits, workgroups per CU and the non-temporal threshold follow the MATRIX's element size)
+// the executor of gemv_any_plan (gemv_plan.hip: cut, chunks of grid.z, workspace, the non-temporal switch, the tag and the two refusals). V != T: wg_gemv_mixed
+template <typename T, typename V = T>
 int launch_any(wg_ctx *ctx, bool trans, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, void *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v) {
-    constexpr uint32_t E = Elt<T>::E;
-    const uint32_t cus = ctx->compute_units > 0 ? (uint32_t)ctx->compute_units : 256u;
-    const uint64_t gz = (uint64_t)nmats * nrhs;
-    if (gz > 0xffffffffull) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemv: matrices x right-hand sides = %llu exceeds 2^32 - 1", (unsigned long long)gz);
-    const uint32_t zchunk = gz < 65535u ? (uint32_t)gz : 65535u; // grid.z (grid.y of the combine pass) per launch: the pairs go in chunks of up to 65535
-    const uint32_t out_len = trans ? C : R;
+    wg_gemv_query q = {};
+    q.trans = trans; q.rows_out = trans ? C : R; q.k = trans ? R : C; q.nrhs = nrhs; q.nmats = nmats;
+    q.m_elem = sizeof(T); q.v_elem = sizeof(V);
+    q.cus = (uint32_t)wg_ctx_cus(ctx);
+    const wg_gemv_any_plan p = gemv_any_plan(q);
+    if (!p.launch) return p.status ? wg_set_error(p.status, "%s", p.message) : WG_OK;
+    const uint32_t out_len = q.rows_out;
     AnyArgs a;
     a.m = (uintptr_t)m.ptr; a.ldm = m.ld; a.m_batch = m.batch;
     a.v = (uintptr_t)v.ptr; a.ldv = v.ld; a.v_batch = v.batch;
     a.out = (uintptr_t)out; a.ldo = out_ld; a.o_batch = out_batch;
     a.R = R; a.C = C; a.nrhs = nrhs; a.part = nullptr; a.zbase = 0;
-    // ~per_cu workgroups per CU; a split is whole 64-column chunks (N) / whole 64 E-row steps (T)
-    const uint32_t gx = trans ? (C + 4u * kWaves - 1u) / (4u * kWaves) : (R + 64u * E - 1u) / (64u * E);
-    const uint32_t unit = trans ? 64u * E : 64u * kWaves, len = trans ? R : C, units = (len + unit - 1u) / unit;
-    const uint64_t per_cu = WG_ANY_PER_CU ? WG_ANY_PER_CU : (!trans && (uint64_t)R * C * sizeof(T) >= (1ull << 30) ? 4u : 2u);
-    uint32_t nsplit = (uint32_t)((per_cu * cus + (uint64_t)gx * gz - 1u) / ((uint64_t)gx * gz));
-    if (nsplit > units) nsplit = units;
-    if (nsplit < 1u) nsplit = 1u;
-    a.per_split = ((units + nsplit - 1u) / nsplit) * unit;
-    nsplit = (len + a.per_split - 1u) / a.per_split;
-    if (nsplit > 65535u) return wg_set_error(WG_ERR_UNSUPPORTED, "Gemv: too many splits");
-    a.nsplit = nsplit;
-    if (nsplit > 1u) {
+    a.per_split = p.per_split;
+    a.nsplit = p.nsplit;
+    if (p.nsplit > 1u) {
         void *ws = nullptr;
-        if (int rc = wg_ctx_workspace(ctx, (size_t)zchunk * nsplit * out_len * sizeof(float), &ws)) return rc; // (one chunk's partials: the chunks run in stream order)
+        if (int rc = wg_ctx_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
         a.part = (float *)ws;
     }
-    const bool nt = (uint64_t)R * C * sizeof(T) >= (512ull << 20);
-    const uint32_t nchunks = (uint32_t)((gz + zchunk - 1u) / zchunk);
-    if (nchunks > 1u) wg_path(ctx, "gemv_any/%s,ns=%u,chunks=%u", trans ? "t" : "n", nsplit, nchunks);
-    else wg_path(ctx, "gemv_any/%s,ns=%u", trans ? "t" : "n", nsplit);
-    for (uint64_t base = 0; base < gz; base += zchunk) {
+    wg_path(ctx, "%s", p.tag);
+    const uint64_t gz = (uint64_t)nmats * nrhs;
+    for (uint64_t base = 0; base < gz; base += p.zchunk) {
         a.zbase = (uint32_t)base;
-        const uint32_t nz = gz - base < zchunk ? (uint32_t)(gz - base) : zchunk;
-        const dim3 grid(gx, nsplit, nz), block(kThreads);
+        const uint32_t nz = gz - base < p.zchunk ? (uint32_t)(gz - base) : p.zchunk;
+        const dim3 grid(p.grid_x, p.nsplit, nz), block(kThreads);
         if (trans) {
-            if (nt) hipLaunchKernelGGL((gemv_any_t_kernel<T, true, V>), grid, block, 0, ctx->stream, a);
+            if (p.nt) hipLaunchKernelGGL((gemv_any_t_kernel<T, true, V>), grid, block, 0, ctx->stream, a);
             else hipLaunchKernelGGL((gemv_any_t_kernel<T, false, V>), grid, block, 0, ctx->stream, a);
-        } else if (nt) hipLaunchKernelGGL((gemv_any_n_kernel<T, true, V>), grid, block, 0, ctx->stream, a);
+        } else if (p.nt) hipLaunchKernelGGL((gemv_any_n_kernel<T, true, V>), grid, block, 0, ctx->stream, a);
         else hipLaunchKernelGGL((gemv_any_n_kernel<T, false, V>), grid, block, 0, ctx->stream, a);
         WG_HIP_TRY(hipGetLastError());
-        if (nsplit > 1u) {
+        if (p.nsplit > 1u) {
             hipLaunchKernelGGL(gemv_any_combine_kernel<V>, dim3((out_len + kThreads - 1u) / kThreads, nz), block, 0, ctx->stream, a, out_len);
             WG_HIP_TRY(hipGetLastError());
         }
@@ -264,7 +253,6 @@ int launch_any(wg_ctx *ctx, bool trans, uint32_t R, uint32_t C, uint32_t nrhs, u
 // m: the R x C view as stored (GemvTr contracts its rows); v / out: nrhs columns, v.ld / out_ld apart.
 int wgk_gemv_any(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, void *out, uint32_t out_ld, uint64_t out_batch,
                  wgk_mat m, wgk_mat v) {
-    if (R == 0 || C == 0 || nrhs == 0 || nmats == 0) return WG_OK;
     if (dtype == WG_F16) return launch_any<_Float16>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
     if (dtype == WG_BF16) return launch_any<wg_bf16>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
     return launch_any<float>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
@@ -273,7 +261,6 @@ int wgk_gemv_any(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t R, uint32_t C
 // wg_gemv_mixed on a matrix view of any alignment: m holds m_dtype (f16 / bf16) elements, v and out f32
 int wgk_gemv_any_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld, uint64_t out_batch,
                        wgk_mat m, wgk_mat v) {
-    if (R == 0 || C == 0 || nrhs == 0 || nmats == 0) return WG_OK;
     if (m_dtype == WG_F16) return launch_any<_Float16, float>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
     return launch_any<wg_bf16, float>(ctx, trans, R, C, nrhs, nmats, out, out_ld, out_batch, m, v);
 }

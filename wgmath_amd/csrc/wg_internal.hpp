@@ -185,7 +185,7 @@ int wgk_gemv(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t rows_out, uint32_
              void *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v);
 
 // out (M x N) = op(m1) (M x K) * m2 (K x N); trans: m1 stored K x M
-// fused Gemv + Reduce (one launch) for launch-bound sizes; WG_ERR_UNSUPPORTED (no error message) = not that shape family
+// fused Gemv + Reduce (one launch) for launch-bound sizes: wgk_gemv_small_reduce below
 // Gemv / GemvTr on a matrix view of any alignment (gemv_any.hip): m is the R x C view as stored, v / out hold nrhs columns
 int wgk_gemv_any(wg_ctx *ctx, bool trans, wg_dtype dtype, uint32_t R, uint32_t C, uint32_t nrhs, uint32_t nmats, void *out, uint32_t out_ld, uint64_t out_batch,
                  wgk_mat m, wgk_mat v);
@@ -200,7 +200,12 @@ int wgk_gemv_any_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t R, ui
 // contraction, grid and workspace are the plan's (gemv_q8_plan.hip); ld / batch strides count each operand's own elements.
 int wgk_gemv_q8(wg_ctx *ctx, const wg_gemv_q8_plan &p, bool trans, uint32_t group_rows, uint32_t rows, uint32_t cols, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld,
                 uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat v);
-int wgk_gemv_small_reduce(wg_ctx *ctx, int op, uint32_t rows_out, uint32_t k, float *y, wgk_mat m, wgk_mat v, unsigned *counter, float *result);
+// The Gemv launchers' query (gemv_plan.hpp: they ask gemv_plan and do what the plan says) of a call on these views in this context; m_dtype / v_dtype: the elements of
+// the matrix and of the vectors / the result; gemm16: wg_gemv on 16-bit elements, which the 16-bit Gemm kernels may take
+wg_gemv_query wgk_gemv_query(const wg_ctx *ctx, bool trans, wg_dtype m_dtype, wg_dtype v_dtype, bool gemm16, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats,
+                             uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat v);
+// p: the plan of the same f32 Gemv with one matrix and one vector, leaf WG_GEMV_SMALL (the caller asks gemv_plan and keeps every other call on two launches)
+int wgk_gemv_small_reduce(wg_ctx *ctx, const wg_gemv_plan &p, int op, uint32_t rows_out, uint32_t k, float *y, wgk_mat m, wgk_mat v, unsigned *counter, float *result);
 
 int wgk_gemm_f32(wg_ctx *ctx, bool trans, uint32_t M, uint32_t N, uint32_t K, uint32_t nmats,
                  float *out, uint32_t out_ld, uint64_t out_batch, wgk_mat m1, wgk_mat m2, float alpha = 1.f, float beta = 0.f);
