@@ -429,6 +429,20 @@ struct Gemm {
     void dispatch_out32_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<W> m1, GpuTensorView<W> m2) const {
         dispatch_out32_generic(d, s, p, out, m1, m2, GemmVariant::GemmTr);
     }
+    // extension (wg_gemm_q8): Gemv::dispatch_q8_tr's int8 weights and f32 group scales (k x outputs; scales: ceil(k / group_rows) x outputs x mats) against 16-bit
+    // columns x (X = _Float16 / bf16, k x N) with an f32 result out (outputs x N) = W^T x on the matrix cores. Only the transposed variants exist (the library
+    // refuses Gemm / GemmFast, and X = float). Column-major views (the row-major surface has no q8 form).
+    template <typename X>
+    void dispatch_q8_generic(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<float> out, GpuTensorView<int8_t> m, GpuTensorView<float> scales,
+                             GpuTensorView<X> x, uint32_t group_rows, GemmVariant variant = GemmVariant::GemmTr) const {
+        check(wg_gemm_q8(pass.ctx(), (wg_gemm_variant)variant, group_rows, dtype_of<X>::value, out.buffer(), out.shape(), m.buffer(), m.shape(), scales.buffer(),
+                         scales.shape(), x.buffer(), x.shape()));
+    }
+    template <typename X>
+    void dispatch_q8_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<int8_t> m, GpuTensorView<float> scales,
+                        GpuTensorView<X> x, uint32_t group_rows) const {
+        dispatch_q8_generic(d, s, p, out, m, scales, x, group_rows, GemmVariant::GemmTr);
+    }
 };
 
 // gemv.rs:9-137

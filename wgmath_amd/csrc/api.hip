@@ -5,6 +5,7 @@
 #include "wg_internal.hpp"
 #include "views_overlap.hpp"
 #include "gemv_q8_plan.hpp"
+#include "gemm_q8_plan.hpp"
 #include "gemv_plan.hpp"
 
 namespace {
@@ -464,6 +465,55 @@ int wg_gemv_q8(wg_ctx *ctx, wg_gemv_variant variant, uint32_t group_rows, wg_buf
     const wg_gemv_q8_plan p = gemv_q8_plan(q);
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_gemv_q8(ctx, p, tr, group_rows, mm.rows, mm.cols, o.cols, o.mats, O, o.stride, o.stride_mat, M, S, V);
+}
+
+// wg_gemm on wg_gemv_q8's int8 matrix and scales with 16-bit columns (include/wgebra_hip.h): wg_gemm_out32's checks in its order with its messages, then wg_gemv_q8's
+// checks of group_rows and of the scales' shape behind the dimension check; bounds with 1 / 4 / 2 / 4 bytes per element of m / scales / x / out; `out` against `m` in
+// 1-byte and against `x` in 2-byte units. The kernels are the plan's (gemm_q8_plan.hip).
+int wg_gemm_q8(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dtype x_dtype, wg_buf *out, wg_view_shape out_shape, const wg_buf *m, wg_view_shape m_shape,
+               const wg_buf *scales, wg_view_shape scales_shape, const wg_buf *x, wg_view_shape x_shape) {
+    const wg_buf *bufs[4] = { out, m, scales, x };
+    if (int rc = check_common("Gemm", ctx, x_dtype, bufs, 4)) return rc;
+    if (x_dtype == WG_F32)
+        return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: wg_gemm_q8 takes f16 or bf16 columns (f32 activations stay with wg_gemv_q8, which never narrows them)");
+    if ((int)variant < 0 || (int)variant > 3) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: unknown variant %d", (int)variant);
+    if (variant != WG_GEMM_TR && variant != WG_GEMM_TR_FAST)
+        return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: wg_gemm_q8 computes out = W^T x only (WG_GEMM_TR); wg_gemv_q8 computes out = W v, whose scales cannot leave the contraction");
+    const View o = mk(out_shape), mm = mk(m_shape), ss = mk(scales_shape), xx = mk(x_shape);
+
+    if (mm.rows != xx.rows || mm.cols != o.rows || o.cols != xx.cols || o.mats != mm.mats || o.mats != xx.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemm: dimension mismatch. (out [%u,%u,%u], m1 [%u,%u,%u]^T, m2 [%u,%u,%u])", o.rows, o.cols, o.mats, mm.rows, mm.cols,
+                            mm.mats, xx.rows, xx.cols, xx.mats);
+    if (group_rows == 0 || (group_rows % 16u != 0 && group_rows < mm.rows))
+        return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: group_rows %u is neither a positive multiple of 16 nor at least the %u rows of m", group_rows, mm.rows);
+    const uint32_t s_rows = mm.rows / group_rows + (mm.rows % group_rows != 0);
+    if (ss.rows != s_rows || ss.cols != mm.cols || ss.mats != mm.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemm: dimension mismatch. (m [%u,%u,%u], group_rows %u, scales [%u,%u,%u], expected [%u,%u,%u])", mm.rows, mm.cols, mm.mats,
+                            group_rows, ss.rows, ss.cols, ss.mats, s_rows, mm.cols, mm.mats);
+    if (out->bytes == 0 || m->bytes == 0 || scales->bytes == 0 || x->bytes == 0) return WG_OK;
+    if (o.rows == 0 || o.cols == 0 || o.mats == 0) return WG_OK;
+
+    if (int rc = check_bounds("Gemm", "out", o, out, WG_F32)) return rc;
+    if (int rc = check_bounds_es("Gemm", "m", mm, m, 1)) return rc;
+    if (int rc = check_bounds("Gemm", "scales", ss, scales, WG_F32)) return rc;
+    if (int rc = check_bounds("Gemm", "x", xx, x, x_dtype)) return rc;
+    if (int rc = check_alias_f32_u8("Gemm", "out", o, out->ptr, "m", mm, m->ptr)) return rc;
+    if (int rc = check_alias("Gemm", WG_F32, "out", o, out->ptr, "scales", ss, scales->ptr)) return rc;
+    if (int rc = check_alias_f32_u16("Gemm", "out", o, out->ptr, "x", xx, x->ptr)) return rc;
+
+    const wgk_mat M = { (const char *)m->ptr + mm.offset, mm.stride, mm.stride_mat };
+    const wgk_mat S = { elem_ptr(scales, ss.offset, WG_F32), ss.stride, ss.stride_mat };
+    const wgk_mat X = { elem_ptr(x, xx.offset, x_dtype), xx.stride, xx.stride_mat };
+    float *O = (float *)elem_ptr(out, o.offset, WG_F32);
+    wg_gemm_q8_query q = {};
+    q.k = mm.rows; q.outputs = mm.cols; q.n = o.cols; q.mats = o.mats; q.group_rows = group_rows; q.x_bf16 = x_dtype == WG_BF16;
+    q.ldm = mm.stride; q.lds = ss.stride; q.ldx = xx.stride; q.ldo = o.stride;
+    q.m_batch = mm.stride_mat; q.s_batch = ss.stride_mat; q.x_batch = xx.stride_mat; q.o_batch = o.stride_mat;
+    q.m_addr16 = (uint32_t)((uintptr_t)M.ptr % 16u); q.x_addr16 = (uint32_t)((uintptr_t)X.ptr % 16u); q.o_addr16 = (uint32_t)((uintptr_t)O % 16u);
+    q.cus = (uint32_t)wg_ctx_cus(ctx);
+    const wg_gemm_q8_plan p = gemm_q8_plan(q);
+    WG_HIP_TRY(hipSetDevice(ctx->device));
+    return wgk_gemm_q8(ctx, p, x_dtype == WG_BF16, group_rows, mm.rows, mm.cols, o.cols, o.mats, O, o.stride, o.stride_mat, M, S, X);
 }
 
 int wg_reduce(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype, const wg_buf *value, wg_view_shape value_shape, wg_buf *result) {

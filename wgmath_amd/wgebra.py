@@ -76,6 +76,18 @@ def _q8_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView, v: G
             raise TypeError(f"q8 Gemv: `{name}` must be float32, got {x._tensor.dtype} (`m` carries the int8 weights)")
 
 
+def _gemm_q8_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView, x: GpuTensorView) -> int:
+    """The wg_dtype of `x` in a q8 Gemm: `m` int8, `scales` and `out` float32, `x` float16 or bfloat16 -- anything else is a TypeError."""
+    if np.dtype(m._tensor.dtype) != np.dtype(np.int8):
+        raise TypeError(f"q8 Gemm: `m` must be int8, got {m._tensor.dtype}")
+    for name, t in (("scales", scales), ("out", out)):
+        if np.dtype(t._tensor.dtype) != np.dtype(np.float32):
+            raise TypeError(f"q8 Gemm: `{name}` must be float32, got {t._tensor.dtype} (`m` carries the int8 weights)")
+    if np.dtype(x._tensor.dtype) == np.dtype(np.float32):
+        raise TypeError("q8 Gemm: `x` must be float16 or bfloat16 (float32 activations are Gemv.dispatch_q8*)")
+    return wg_dtype(x._tensor.dtype)  # (float16 or bfloat16: every other element type is a TypeError there)
+
+
 def _q8_groups(rows: int, group_rows: int) -> int:
     group_rows = int(group_rows)
     if group_rows <= 0 or (group_rows % 16 and group_rows < rows):
@@ -190,6 +202,23 @@ class Gemm:
         check(lib.wg_gemm_out32(pass_._ctx.handle, int(variant), dt, float(alpha), float(beta),
                                 out.buffer()._h, out.shape().to_c(), m1.buffer()._h, m1.shape().to_c(),
                                 m2.buffer()._h, m2.shape().to_c()))
+
+    def dispatch_q8_tr(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, x, group_rows: int) -> None:
+        self.dispatch_q8_generic(device, shapes, pass_, out, m, scales, x, group_rows, GemmVariant.GemmTr)
+
+    def dispatch_q8_generic(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, x, group_rows: int,
+                            variant: GemmVariant = GemmVariant.GemmTr) -> None:
+        """Extension (`wg_gemm_q8`): `Gemv.dispatch_q8_tr`'s int8 matrix and float32 group scales (`quantize_q8`'s layout, k x outputs) against float16 / bfloat16
+        columns `x` (k x N) with a float32 `out` (outputs x N) = W^T x on the matrix cores. int8 is widened exactly, nothing is narrowed, the scale enters per
+        group in f32. Only the transposed variants exist (Gemm / GemmFast are refused by the library). Column-major views only (the row-major surface has no q8
+        form)."""
+        out, m, scales, x = as_view(out, 3), as_view(m, 3), as_view(scales, 3), as_view(x, 3)
+        xd = _gemm_q8_dtypes(out, m, scales, x)
+        if self.row_major:
+            raise TypeError("Gemm.dispatch_q8*: the row-major operator surface has no q8 form")
+        check(lib.wg_gemm_q8(pass_._ctx.handle, int(variant), int(group_rows), xd,
+                             out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
+                             scales.buffer()._h, scales.shape().to_c(), x.buffer()._h, x.shape().to_c()))
 
 
 class Gemv:
