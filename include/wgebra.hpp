@@ -494,6 +494,19 @@ struct Gemv {
                         GpuTensorView<float> v, uint32_t group_rows) const {
         dispatch_q8_generic(d, s, p, out, m, scales, v, group_rows, GemvVariant::GemvTr);
     }
+    // extension (wg_gemv_q4): packed 4-bit weights -- m holds BYTES, k / 2 x outputs; byte j of a column carries logical row 2 j in its low and row 2 j + 1 in its high
+    // nibble, each as q + 8 with q in -8 .. 7 -- with one f32 scale per group_rows consecutive logical rows of a column (scales: ceil(k / group_rows) x outputs x mats),
+    // f32 vectors (k rows) and an f32 result: out = W^T v with W = scales[r / group_rows, c] * q[r, c]. Only the transposed variants exist (the library refuses Gemv /
+    // GemvFast). Column-major views (the row-major surface has no q4 form).
+    void dispatch_q4_generic(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<float> out, GpuTensorView<uint8_t> m, GpuTensorView<float> scales,
+                             GpuTensorView<float> v, uint32_t group_rows, GemvVariant variant = GemvVariant::GemvTr) const {
+        check(wg_gemv_q4(pass.ctx(), (wg_gemv_variant)variant, group_rows, out.buffer(), out.shape(), m.buffer(), m.shape(), scales.buffer(), scales.shape(), v.buffer(),
+                         v.shape()));
+    }
+    void dispatch_q4_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<uint8_t> m, GpuTensorView<float> scales,
+                        GpuTensorView<float> v, uint32_t group_rows) const {
+        dispatch_q4_generic(d, s, p, out, m, scales, v, group_rows, GemvVariant::GemvTr);
+    }
 };
 
 // reduce.rs:62-113

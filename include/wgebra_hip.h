@@ -56,6 +56,7 @@ extern "C" {
                                     that was valid keeps its meaning, dtype 2 used to be WG_ERR_INVALID_ARG -- so no bump); wg_gemv_mixed (an added symbol); wg_gemm_out32 with wg_debug_gemm_out32_query (added symbols);
                                     wg_gemv_q8 with wg_debug_gemv_q8_plan and its two structs (added symbols; wg_dtype is unchanged);
                                     wg_gemm_q8 with wg_debug_gemm_q8_plan and its two structs (added symbols; wg_dtype is unchanged);
+                                    wg_gemv_q4 with wg_debug_gemv_q4_plan and its two structs (added symbols; wg_dtype is unchanged);
                                     wg_debug_gemv_plan and wg_debug_gemv_any_plan with wg_gemv_query and their plan structs (added diagnostic symbols);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
@@ -388,6 +389,37 @@ typedef struct wg_gemv_q8_plan {
 } wg_gemv_q8_plan;
 /* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the combine pass of a cut included. */
 int wg_debug_gemv_q8_plan(const wg_gemv_q8_query *query, wg_gemv_q8_plan *plan, char *tags, size_t cap);
+/* The same for wg_gemv_q4's launcher (gemv_q4_plan.hip). The matrix's sizes and strides count BYTES (two weights each): the contraction length is k = 2 * rows.
+ * Sizes and strides of the other operands count f32 elements; *_addr16: the byte address of the view's first element modulo 16. */
+typedef struct wg_gemv_q4_query {
+    uint32_t trans;                          /* 1: out = W^T v (GemvTr, GemvTrFast), the product there is; 0: out = W v, which the plan refuses */
+    uint32_t rows, cols, nrhs, mats;         /* the matrix as stored: rows in BYTES (k / 2) x cols; right-hand sides and matrices (taken from `out`) */
+    uint32_t group_rows;                     /* as passed: a positive multiple of 32, or any value >= k */
+    uint32_t ldm, lds, ldv, ldo;             /* leading dimensions of m (bytes), scales, v and out */
+    uint64_t m_batch, s_batch, v_batch, o_batch; /* matrix strides (m: bytes) */
+    uint32_t m_addr16, v_addr16;             /* byte address of the first element of m and of v, modulo 16 (scales and out are reached 4 bytes at a time: any view) */
+    uint32_t cus;                            /* compute units of the context's stream */
+} wg_gemv_q4_query;
+typedef enum wg_gemv_q4_leaf {
+    WG_GEMV_Q4_NOTHING = 0,      /* no output element: no launch, WG_OK */
+    WG_GEMV_Q4_UNSUPPORTED = 1,  /* no launch: the call returns `status` with `message` */
+    WG_GEMV_Q4_T = 2,            /* out = W^T v, a half-wave per column or per 4 adjacent columns, 16-byte loads of 32 weights (gemv_q4_t_kernel) */
+    WG_GEMV_Q4_ANY_T = 3         /* out = W^T v a byte (two weights) at a time: any view */
+} wg_gemv_q4_leaf;
+typedef struct wg_gemv_q4_plan {
+    uint32_t leaf;                           /* wg_gemv_q4_leaf */
+    uint32_t rhs_tile, rhs_groups;           /* right-hand sides per pass over the matrix in registers (1, 2, 4, 8); groups of 8 right-hand sides on grid.z */
+    uint32_t loads, cols;                    /* WG_GEMV_Q4_T: 16-byte loads in flight per lane and column (a trip is 1024 * loads logical rows) and adjacent columns per
+                                                half-wave (1 or 4: they share the vectors' pieces) */
+    uint32_t nsplit, k_per_split;            /* cut of the contraction over grid.y in LOGICAL rows (1, k: none); no empty split, every boundary a multiple of 1024 */
+    uint32_t out_per_block;                  /* outputs a workgroup owns: block b takes [b * out_per_block, (b + 1) * out_per_block) */
+    uint32_t grid[3], block;                 /* the launch: grid = (output blocks, splits, mats * rhs_groups) */
+    uint64_t workspace_bytes;                /* f32 partials of a cut: mats * nsplit * nrhs * outputs * 4 (the context's workspace), 0 without a cut */
+    int32_t status;                          /* WG_GEMV_Q4_NOTHING / _UNSUPPORTED */
+    char message[128];
+} wg_gemv_q4_plan;
+/* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the combine pass of a cut included. */
+int wg_debug_gemv_q4_plan(const wg_gemv_q4_query *query, wg_gemv_q4_plan *plan, char *tags, size_t cap);
 /* The same for wg_gemm_q8's launcher (gemm_q8_plan.hip): leaf, column tile, cut of the contraction, grid and workspace bytes as a pure function of the query. Sizes
  * and strides count each operand's own elements (1 byte for `m`, 2 for `x`, 4 for `scales` and `out`); *_addr16: the byte address of the view's first element
  * modulo 16. */
@@ -634,6 +666,53 @@ int wg_gemv_q8(wg_ctx *ctx, wg_gemv_variant variant, uint32_t group_rows,
                const wg_buf *m, wg_view_shape m_shape,           /* int8_t, column-major like every view */
                const wg_buf *scales, wg_view_shape scales_shape, /* f32: ceil(m.rows / group_rows) x m.cols x mats */
                const wg_buf *v, wg_view_shape v_shape);          /* f32 */
+
+/*
+ * Extension: GemvTr on packed 4-bit weights with group scales -- the decode product on weights stored as in Q4_0, or GPTQ / AWQ without zero points: half the bytes
+ * of wg_gemv_q8. out = W^T v, for every right-hand side and matrix of `out`; no alpha, no beta.
+ * The operand: `m` holds packed BYTES, column-major like every view. Byte j of a column holds logical row 2 j in its LOW nibble and row 2 j + 1 in its HIGH nibble. A
+ * nibble n in 0 .. 15 stands for the integer q = n - 8, so q is in -8 .. 7 and all 16 values are legal. W[r, c, z] = scales[r / G, c, z] * (float)q[r, c, z] with
+ * G = group_rows: one f32 scale per G consecutive LOGICAL rows of a column; groups run along the contraction, as in wg_gemv_q8. m_shape counts BYTES: rows, leading
+ * dimension, offset and matrix stride. The contraction length is k = 2 * m.rows. `scales` holds f32, ceil(k / G) x m.cols x mats; `v` holds f32 with k rows; `out`
+ * holds f32 with m.cols rows. Right-hand sides and matrices are taken from `out`. The bounds checks use 1 byte for `m` and 4 bytes for the others. Scales stay in a
+ * tensor of their own, as for wg_gemv_q8: repacking another container's block layout is a host permutation and not part of this call. wg_dtype has no 4-bit value
+ * and gets none.
+ *   variant       : WG_GEMV_TR is the product above; WG_GEMV_TR_FAST is the same call. WG_GEMV and WG_GEMV_FAST would put the groups and the nibble pairs along the
+ *                   outputs, a layout nobody stores: WG_ERR_UNSUPPORTED ("... wg_gemv_q8 computes out = W v ..."). The refusal comes right behind the checks of
+ *                   the context, the buffers and the variant's range, BEFORE any dimension, group_rows or size is looked at: a mismatched or a zero-sized call
+ *                   with these variants is WG_ERR_UNSUPPORTED too, not WG_ERR_DIM_MISMATCH or WG_OK (wg_gemm_q8's refused out = W x does the same).
+ *   group_rows    : a positive multiple of 32, or any positive value >= k (one scale per output: `scales` has one row). Anything else is WG_ERR_INVALID_ARG.
+ *   DIM_MISMATCH  : v.rows != 2 * m.rows or out.rows != m.cols ("Gemv: dimension mismatch. (out [..], m [..]^T packed: k K, v [..])"); then `scales` of another shape
+ *                   than the one above ("Gemv: dimension mismatch. (m [..] packed: k K, group_rows G, scales [..], expected [..])").
+ * Everything else is wg_gemv_q8's contract, in its order, with its status codes and messages: the NULL context ("Gemv: ctx is NULL"), NULL buffers, the unknown
+ * variant, zero-sized buffers / views skipped with WG_OK, views that exceed their buffer, nmats * ceil(nrhs / 8) > 65535 (UNSUPPORTED), WG_ERR_WORKSPACE when the
+ * partials of a cut contraction would have to grow the context's workspace inside a recording.
+ * Arithmetic:
+ *   - q = n - 8 is formed exactly (an f32 integer) before anything is multiplied: the -8 is NOT folded into a per-piece correction (sum n v - 8 sum v would leave
+ *     rounding residue of the size of 8 |s v| under a zero weight). `v` and `scales` are read as the f32 they are and never narrowed; every operation is an f32 FMA
+ *     or multiply; the f32 accumulator is stored as it is. Nothing is flushed: subnormal scales, vector entries and results are kept.
+ *   - where the scale enters (each of the k terms takes at most two f32 roundings either way):
+ *       aligned views (gemv_q4_t_kernel): per PIECE of 16 weights -- half a 16-byte load, logical rows 16 i .. 16 i + 15 --: d = the piece's 16 products q * v
+ *         summed by sequential FMAs from zero in row order, then acc = fmaf(scale, d, acc). A piece never straddles a group. The unscaled d must be finite for a
+ *         finite result (|q| <= 8: no concern below 1e36);
+ *       any other view (gemv_q4_any_t_kernel): per ELEMENT -- w = scale * q (the dequantised weight), then acc = fmaf(w, v, acc).
+ *   - Inf and NaN behave as in the f32 product of the dequantised matrix with `v`: 0 * Inf is NaN (a zero scale against an Inf in `v`, a zero weight against it), and
+ *     a NaN reaches exactly the outputs whose sums contain it; load slots past the end of a range contribute nothing. `out` is overwritten.
+ *   - deterministic: no atomics; a cut contraction writes f32 partials that one pass adds in a fixed order -- two calls give identical bits.
+ * Which kernels (gemv_q4_plan.hip, wg_debug_gemv_q4_plan): the streaming kernel takes views where m.rows % 16 == 0 (k % 32 == 0), the matrix's first byte, leading
+ * dimension and matrix stride are multiples of 16 bytes, and `v` is vec4-aligned (address, leading dimension and matrix stride multiples of 16 bytes where they
+ * count); `scales` and `out` are reached one float at a time and may be any view. Every other view runs where it lies on the element-by-element kernel -- correct,
+ * not fast, and without any copy of the matrix. Up to 8 right-hand sides share one pass over the matrix; more run as groups of 8 on grid.z.
+ *   ALIASED       : `out` shares a byte with the part of `m`, of `scales` or of `v` the call addresses -- on addresses, `out` against `m` in 1-byte units, so both may
+ *                   live in one buffer: touching is legal, one shared byte is refused. The read operands may overlap each other.
+ * wg_debug_take_path: tags begin "gemv_q4/": "gemv_q4/t,nr=1,u=2,c=4,ns=1" (right-hand-side tile, loads in flight per column, columns per half-wave, splits),
+ * "gemv_q4/combine,ns=4", "gemv_q4/any_t".
+ */
+int wg_gemv_q4(wg_ctx *ctx, wg_gemv_variant variant, uint32_t group_rows,
+               wg_buf *out, wg_view_shape out_shape,             /* f32: m.cols rows */
+               const wg_buf *m, wg_view_shape m_shape,           /* packed bytes, two weights each: k / 2 x outputs x mats, column-major */
+               const wg_buf *scales, wg_view_shape scales_shape, /* f32: ceil(k / group_rows) x m.cols x mats */
+               const wg_buf *v, wg_view_shape v_shape);          /* f32: k = 2 * m.rows rows */
 
 /*
  * Extension: Gemm on 16-bit operands with an f32 result -- out = alpha * op(m1) * m2 + beta * out with the f32 accumulators of the matrix cores stored as they

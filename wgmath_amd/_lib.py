@@ -90,6 +90,23 @@ class GemvQ8PlanC(ctypes.Structure):
                 + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
 
 
+class GemvQ4QueryC(ctypes.Structure):
+    """wg_gemv_q4_query: everything wg_gemv_q4's choice of kernel, cut and grid depends on (wg_debug_gemv_q4_plan). `rows`, `ldm` and `m_batch` count bytes."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("trans", "rows", "cols", "nrhs", "mats", "group_rows", "ldm", "lds", "ldv", "ldo")]
+                + [(n, ctypes.c_uint64) for n in ("m_batch", "s_batch", "v_batch", "o_batch")]
+                + [(n, ctypes.c_uint32) for n in ("m_addr16", "v_addr16", "cus")])
+
+
+GEMV_Q4_LEAVES = ("nothing", "unsupported", "t", "any_t")  # wg_gemv_q4_leaf
+
+
+class GemvQ4PlanC(ctypes.Structure):
+    """wg_gemv_q4_plan: the leaf (index into GEMV_Q4_LEAVES) and what it is launched with; `k_per_split` counts logical rows."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("leaf", "rhs_tile", "rhs_groups", "loads", "cols", "nsplit", "k_per_split", "out_per_block")]
+                + [("grid", ctypes.c_uint32 * 3), ("block", ctypes.c_uint32), ("workspace_bytes", ctypes.c_uint64)]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
+
+
 class GemmQ8QueryC(ctypes.Structure):
     """wg_gemm_q8_query: everything wg_gemm_q8's choice of kernel, column tile, cut and grid depends on (wg_debug_gemm_q8_plan)."""
     _fields_ = ([(n, ctypes.c_uint32) for n in ("k", "outputs", "n", "mats", "group_rows", "x_bf16", "ldm", "lds", "ldx", "ldo")]
@@ -218,6 +235,8 @@ def _load() -> ctypes.CDLL:
         "wg_gemv_mixed": (ci, [vp, ci, ci, vp, S, vp, S, vp, S]),
         "wg_gemv_q8": (ci, [vp, ci, u32, vp, S, vp, S, vp, S, vp, S]),
         "wg_debug_gemv_q8_plan": (ci, [ctypes.POINTER(GemvQ8QueryC), ctypes.POINTER(GemvQ8PlanC), cp, sz]),
+        "wg_gemv_q4": (ci, [vp, ci, u32, vp, S, vp, S, vp, S, vp, S]),
+        "wg_debug_gemv_q4_plan": (ci, [ctypes.POINTER(GemvQ4QueryC), ctypes.POINTER(GemvQ4PlanC), cp, sz]),
         "wg_gemm_q8": (ci, [vp, ci, u32, ci, vp, S, vp, S, vp, S, vp, S]),
         "wg_debug_gemm_q8_plan": (ci, [ctypes.POINTER(GemmQ8QueryC), ctypes.POINTER(GemmQ8PlanC), cp, sz]),
         "wg_debug_gemv_plan": (ci, [ctypes.POINTER(GemvQueryC), ctypes.POINTER(GemvPlanC), cp, sz]),

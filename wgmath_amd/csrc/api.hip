@@ -5,6 +5,7 @@
 #include "wg_internal.hpp"
 #include "views_overlap.hpp"
 #include "gemv_q8_plan.hpp"
+#include "gemv_q4_plan.hpp"
 #include "gemm_q8_plan.hpp"
 #include "gemv_plan.hpp"
 
@@ -465,6 +466,59 @@ int wg_gemv_q8(wg_ctx *ctx, wg_gemv_variant variant, uint32_t group_rows, wg_buf
     const wg_gemv_q8_plan p = gemv_q8_plan(q);
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_gemv_q8(ctx, p, tr, group_rows, mm.rows, mm.cols, o.cols, o.mats, O, o.stride, o.stride_mat, M, S, V);
+}
+
+// GemvTr on packed 4-bit weights with f32 group scales (include/wgebra_hip.h): wg_gemv_q8's checks in its order with its messages; `m` counts bytes (two weights
+// each), so the contraction length is k = 2 m.rows; out = W v is refused behind the variant check. The kernels are the plan's (gemv_q4_plan.hip).
+int wg_gemv_q4(wg_ctx *ctx, wg_gemv_variant variant, uint32_t group_rows, wg_buf *out, wg_view_shape out_shape, const wg_buf *m, wg_view_shape m_shape, const wg_buf *scales,
+               wg_view_shape scales_shape, const wg_buf *v, wg_view_shape v_shape) {
+    const wg_buf *bufs[4] = { out, m, scales, v };
+    if (int rc = check_common("Gemv", ctx, WG_F32, bufs, 4)) return rc;
+    if ((int)variant < 0 || (int)variant > 3) return wg_set_error(WG_ERR_INVALID_ARG, "Gemv: unknown variant %d", (int)variant);
+    const View o = mk(out_shape), mm = mk(m_shape), ss = mk(scales_shape), vv = mk(v_shape);
+    wg_gemv_q4_query q = {};
+    q.trans = variant == WG_GEMV_TR || variant == WG_GEMV_TR_FAST;
+    if (!q.trans) { // (the plan words the refusal)
+        const wg_gemv_q4_plan p = gemv_q4_plan(q);
+        return wg_set_error(p.status, "%s", p.message);
+    }
+    const uint64_t k64 = 2ull * mm.rows;
+    if (k64 != vv.rows || mm.cols != o.rows)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemv: dimension mismatch. (out [%u,%u,%u], m [%u,%u,%u]^T packed: k %llu, v [%u,%u,%u])", o.rows, o.cols, o.mats, mm.rows,
+                            mm.cols, mm.mats, (unsigned long long)k64, vv.rows, vv.cols, vv.mats);
+    const uint32_t k = (uint32_t)k64;
+    if (group_rows == 0 || (group_rows % 32u != 0 && group_rows < k))
+        return wg_set_error(WG_ERR_INVALID_ARG, "Gemv: group_rows %u is neither a positive multiple of 32 nor at least the %u logical rows of m", group_rows, k);
+    const uint32_t s_rows = k / group_rows + (k % group_rows != 0);
+    if (ss.rows != s_rows || ss.cols != mm.cols || ss.mats != mm.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemv: dimension mismatch. (m [%u,%u,%u] packed: k %u, group_rows %u, scales [%u,%u,%u], expected [%u,%u,%u])", mm.rows,
+                            mm.cols, mm.mats, k, group_rows, ss.rows, ss.cols, ss.mats, s_rows, mm.cols, mm.mats);
+    if (out->bytes == 0 || m->bytes == 0 || scales->bytes == 0 || v->bytes == 0) return WG_OK;
+    if (o.rows == 0 || o.cols == 0 || o.mats == 0) return WG_OK;
+
+    const View m_eff = { mm.rows, mm.cols, o.mats, mm.stride, mm.stride_mat, mm.offset };
+    const View s_eff = { ss.rows, ss.cols, o.mats, ss.stride, ss.stride_mat, ss.offset };
+    const View v_eff = { vv.rows, o.cols, o.mats, vv.stride, vv.stride_mat, vv.offset };
+    if (int rc = check_bounds("Gemv", "out", o, out, WG_F32)) return rc;
+    if (int rc = check_bounds_es("Gemv", "m", m_eff, m, 1)) return rc;
+    if (int rc = check_bounds("Gemv", "scales", s_eff, scales, WG_F32)) return rc;
+    if (int rc = check_bounds("Gemv", "v", v_eff, v, WG_F32)) return rc;
+    if (int rc = check_alias_f32_u8("Gemv", "out", o, out->ptr, "m", m_eff, m->ptr)) return rc;
+    if (int rc = check_alias("Gemv", WG_F32, "out", o, out->ptr, "scales", s_eff, scales->ptr)) return rc;
+    if (int rc = check_alias("Gemv", WG_F32, "out", o, out->ptr, "v", v_eff, v->ptr)) return rc;
+
+    const wgk_mat M = { (const char *)m->ptr + mm.offset, mm.stride, mm.stride_mat };
+    const wgk_mat S = { elem_ptr(scales, ss.offset, WG_F32), ss.stride, ss.stride_mat };
+    const wgk_mat V = { elem_ptr(v, vv.offset, WG_F32), vv.stride, vv.stride_mat };
+    float *O = (float *)elem_ptr(out, o.offset, WG_F32);
+    q.rows = mm.rows; q.cols = mm.cols; q.nrhs = o.cols; q.mats = o.mats; q.group_rows = group_rows;
+    q.ldm = mm.stride; q.lds = ss.stride; q.ldv = vv.stride; q.ldo = o.stride;
+    q.m_batch = mm.stride_mat; q.s_batch = ss.stride_mat; q.v_batch = vv.stride_mat; q.o_batch = o.stride_mat;
+    q.m_addr16 = (uint32_t)((uintptr_t)M.ptr % 16u); q.v_addr16 = (uint32_t)((uintptr_t)V.ptr % 16u);
+    q.cus = (uint32_t)wg_ctx_cus(ctx);
+    const wg_gemv_q4_plan p = gemv_q4_plan(q);
+    WG_HIP_TRY(hipSetDevice(ctx->device));
+    return wgk_gemv_q4(ctx, p, group_rows, k, mm.cols, o.cols, o.mats, O, o.stride, o.stride_mat, M, S, V);
 }
 
 // wg_gemm on wg_gemv_q8's int8 matrix and scales with 16-bit columns (include/wgebra_hip.h): wg_gemm_out32's checks in its order with its messages, then wg_gemv_q8's

@@ -200,6 +200,10 @@ int wgk_gemv_any_mixed(wg_ctx *ctx, bool trans, wg_dtype m_dtype, uint32_t R, ui
 // contraction, grid and workspace are the plan's (gemv_q8_plan.hip); ld / batch strides count each operand's own elements.
 int wgk_gemv_q8(wg_ctx *ctx, const wg_gemv_q8_plan &p, bool trans, uint32_t group_rows, uint32_t rows, uint32_t cols, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld,
                 uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat v);
+// wg_gemv_q4 (gemv_q4.hip): out = W^T v; m holds packed bytes (two 4-bit weights each, k / 2 x rows_out as stored; ld / batch in bytes), s the f32 group scales, v and
+// out f32; k counts logical rows. Launch only: the plan is gemv_q4_plan.hip's.
+int wgk_gemv_q4(wg_ctx *ctx, const wg_gemv_q4_plan &p, uint32_t group_rows, uint32_t k, uint32_t rows_out, uint32_t nrhs, uint32_t nmats, float *out, uint32_t out_ld,
+                uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat v);
 // wg_gemm_q8 (gemm_q8.hip): out = W^T x on the same int8 matrix (k x outputs as stored) and scales, x holds f16 / bf16 (k x n), out f32. Launch only: the plan is
 // gemm_q8_plan.hip's; ld / batch strides count each operand's own elements.
 int wgk_gemm_q8(wg_ctx *ctx, const wg_gemm_q8_plan &p, bool bf16, uint32_t group_rows, uint32_t k, uint32_t outputs, uint32_t n, uint32_t nmats, float *out, uint32_t out_ld,

@@ -129,6 +129,85 @@ def dequantize_q8(q, scales, group_rows: int) -> np.ndarray:
     return (scales[idx] * q.astype(np.float32)).astype(np.float32)
 
 
+def _q4_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView, v: GpuTensorView) -> None:
+    """The element types of a q4 call: `m` uint8 (packed bytes), `scales`, `v` and `out` float32 -- anything else is a TypeError."""
+    if np.dtype(m._tensor.dtype) != np.dtype(np.uint8):
+        raise TypeError(f"q4 Gemv: `m` must be uint8 (two packed weights per byte: pack_q4), got {m._tensor.dtype}")
+    for name, x in (("scales", scales), ("v", v), ("out", out)):
+        if np.dtype(x._tensor.dtype) != np.dtype(np.float32):
+            raise TypeError(f"q4 Gemv: `{name}` must be float32, got {x._tensor.dtype} (`m` carries the packed weights)")
+
+
+def _q4_groups(k: int, group_rows: int) -> int:
+    group_rows = int(group_rows)
+    if group_rows <= 0 or (group_rows % 32 and group_rows < k):
+        raise ValueError(f"group_rows {group_rows} is neither a positive multiple of 32 nor at least the {k} logical rows of the matrix")
+    return group_rows
+
+
+def pack_q4(q) -> np.ndarray:
+    """Integers in -8 .. 7 (k x cols, or k x cols x mats; k even) -> the packed uint8 matrix of `Gemv.dispatch_q4*` (k / 2 x ...): byte j of a column holds logical row
+    2 j in its LOW nibble and row 2 j + 1 in its HIGH nibble, each as n = q + 8."""
+    q = np.asarray(q)
+    if not np.issubdtype(q.dtype, np.integer):
+        raise TypeError(f"pack_q4 takes integers, not {q.dtype}")
+    if q.ndim not in (2, 3):
+        raise ValueError("pack_q4 takes a matrix (k x cols) or a cube (k x cols x mats)")
+    if q.shape[0] % 2:
+        raise ValueError(f"pack_q4: {q.shape[0]} rows -- two weights share a byte, the row count must be even")
+    if q.size and (q.min() < -8 or q.max() > 7):
+        raise ValueError("pack_q4: values outside -8 .. 7")
+    n = (q.astype(np.int16) + 8).astype(np.uint8)
+    return (n[0::2] | (n[1::2] << 4)).astype(np.uint8)
+
+
+def unpack_q4(packed) -> np.ndarray:
+    """The inverse of `pack_q4`: packed uint8 (k / 2 x ...) -> int8 in -8 .. 7 (k x ...)."""
+    p = np.asarray(packed)
+    if p.dtype != np.dtype(np.uint8):
+        raise TypeError(f"unpack_q4 takes uint8 bytes, not {p.dtype}")
+    if p.ndim not in (2, 3):
+        raise ValueError("unpack_q4 takes a matrix (k / 2 x cols) or a cube (k / 2 x cols x mats)")
+    q = np.empty((2 * p.shape[0],) + p.shape[1:], np.int8)
+    q[0::2] = (p & 15).astype(np.int8) - 8
+    q[1::2] = (p >> 4).astype(np.int8) - 8
+    return q
+
+
+def quantize_q4(w32, group_rows: int):
+    """float32 weights (k x cols, or k x cols x mats; k even) -> (packed uint8, scales float32) in the layout of `Gemv.dispatch_q4*`: groups of `group_rows` consecutive
+    ROWS of a column share a scale (a partial last group; group_rows >= k: one scale per column). Per group s = fl32(max|w| / 7) and q = clip(rint(w / s), -7, 7)
+    (-8 is never produced); an all-zero group gives s = 0, q = 0. `scales` has ceil(k / group_rows) rows."""
+    w = np.asarray(w32, np.float32)
+    if w.ndim not in (2, 3):
+        raise ValueError("quantize_q4 takes a matrix (k x cols) or a cube (k x cols x mats)")
+    k = w.shape[0]
+    if k % 2:
+        raise ValueError(f"quantize_q4: {k} rows -- two weights share a byte, the row count must be even")
+    g = _q4_groups(k, group_rows)
+    ng = -(-k // g) if k else 0
+    q = np.zeros(w.shape, np.int8)
+    scales = np.zeros((ng,) + w.shape[1:], np.float32)
+    for i in range(ng):
+        blk = w[i * g:(i + 1) * g]
+        s = (np.abs(blk).max(axis=0) / np.float32(7)).astype(np.float32)
+        scales[i] = s
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.rint(blk / s)
+        q[i * g:(i + 1) * g] = np.clip(np.where(s == 0, np.float32(0), r), -7, 7).astype(np.int8)
+    return pack_q4(q), scales
+
+
+def dequantize_q4(packed, scales, group_rows: int) -> np.ndarray:
+    """The float32 matrix `Gemv.dispatch_q4*` multiplies with: w[r, c] = fl32(scales[r // group_rows, c] * q[r, c]), q = unpack_q4(packed)."""
+    q, scales = unpack_q4(packed), np.asarray(scales, np.float32)
+    g = _q4_groups(q.shape[0], group_rows)
+    idx = np.arange(q.shape[0]) // g
+    if scales.shape != (-(-q.shape[0] // g) if q.shape[0] else 0,) + q.shape[1:]:
+        raise ValueError(f"scales of shape {scales.shape} do not belong to {q.shape[0]} x {q.shape[1:]} weights in groups of {g} rows")
+    return (scales[idx] * q.astype(np.float32)).astype(np.float32)
+
+
 def _out32_dtype(out: GpuTensorView, m1: GpuTensorView, m2: GpuTensorView) -> int:
     """The operands' wg_dtype of an f32-output Gemm: `m1` and `m2` share float16 / bfloat16 / float32, `out` is float32 -- anything else is a TypeError."""
     dt = _common_dtype(m1, m2)
@@ -281,6 +360,23 @@ class Gemv:
         if self.row_major:
             raise TypeError("Gemv.dispatch_q8*: the row-major operator surface has no q8 form")
         check(lib.wg_gemv_q8(pass_._ctx.handle, int(variant), int(group_rows),
+                             out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
+                             scales.buffer()._h, scales.shape().to_c(), v.buffer()._h, v.shape().to_c()))
+
+    def dispatch_q4_tr(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, v, group_rows: int) -> None:
+        self.dispatch_q4_generic(device, shapes, pass_, out, m, scales, v, group_rows, GemvVariant.GemvTr)
+
+    def dispatch_q4_generic(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, v, group_rows: int,
+                            variant: GemvVariant = GemvVariant.GemvTr) -> None:
+        """Extension (`wg_gemv_q4`): a uint8 matrix of packed 4-bit weights (`pack_q4` / `quantize_q4`'s layout: k / 2 bytes x outputs) with one float32 scale per
+        `group_rows` consecutive logical rows of a column, float32 vectors and a float32 result: out = W^T v with W = scales[r // group_rows, c] * q[r, c]. The
+        nibbles are widened exactly, nothing is narrowed, sums are f32. Only the transposed variants exist (Gemv / GemvFast are refused by the library).
+        Column-major views only (the row-major surface has no q4 form)."""
+        out, m, scales, v = as_view(out, 3), as_view(m, 3), as_view(scales, 3), as_view(v, 3)
+        _q4_dtypes(out, m, scales, v)
+        if self.row_major:
+            raise TypeError("Gemv.dispatch_q4*: the row-major operator surface has no q4 form")
+        check(lib.wg_gemv_q4(pass_._ctx.handle, int(variant), int(group_rows),
                              out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
                              scales.buffer()._h, scales.shape().to_c(), v.buffer()._h, v.shape().to_c()))
 
