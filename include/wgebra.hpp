@@ -443,6 +443,20 @@ struct Gemm {
                         GpuTensorView<X> x, uint32_t group_rows) const {
         dispatch_q8_generic(d, s, p, out, m, scales, x, group_rows, GemmVariant::GemmTr);
     }
+    // extension (wg_gemm_q4): Gemv::dispatch_q4_tr's packed 4-bit weights -- m holds BYTES, k / 2 x outputs; byte j of a column carries logical row 2 j in its low and
+    // row 2 j + 1 in its high nibble, q = n - 8 -- and f32 group scales (ceil(k / group_rows) x outputs x mats) against 16-bit columns x (X = _Float16 / bf16, k x N)
+    // with an f32 result out (outputs x N) = W^T x on the matrix cores. Only the transposed variants exist (the library refuses Gemm / GemmFast, and X = float).
+    template <typename X>
+    void dispatch_q4_generic(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<float> out, GpuTensorView<uint8_t> m, GpuTensorView<float> scales,
+                             GpuTensorView<X> x, uint32_t group_rows, GemmVariant variant = GemmVariant::GemmTr) const {
+        check(wg_gemm_q4(pass.ctx(), (wg_gemm_variant)variant, group_rows, dtype_of<X>::value, out.buffer(), out.shape(), m.buffer(), m.shape(), scales.buffer(),
+                         scales.shape(), x.buffer(), x.shape()));
+    }
+    template <typename X>
+    void dispatch_q4_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<uint8_t> m, GpuTensorView<float> scales,
+                        GpuTensorView<X> x, uint32_t group_rows) const {
+        dispatch_q4_generic(d, s, p, out, m, scales, x, group_rows, GemmVariant::GemmTr);
+    }
 };
 
 // gemv.rs:9-137

@@ -57,6 +57,7 @@ extern "C" {
                                     wg_gemv_q8 with wg_debug_gemv_q8_plan and its two structs (added symbols; wg_dtype is unchanged);
                                     wg_gemm_q8 with wg_debug_gemm_q8_plan and its two structs (added symbols; wg_dtype is unchanged);
                                     wg_gemv_q4 with wg_debug_gemv_q4_plan and its two structs (added symbols; wg_dtype is unchanged);
+                                    wg_gemm_q4 with wg_debug_gemm_q4_plan and its two structs (added symbols; wg_dtype is unchanged);
                                     wg_debug_gemv_plan and wg_debug_gemv_any_plan with wg_gemv_query and their plan structs (added diagnostic symbols);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
@@ -452,6 +453,38 @@ typedef struct wg_gemm_q8_plan {
 } wg_gemm_q8_plan;
 /* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the combine pass of a cut included. */
 int wg_debug_gemm_q8_plan(const wg_gemm_q8_query *query, wg_gemm_q8_plan *plan, char *tags, size_t cap);
+/* The same for wg_gemm_q4's launcher (gemm_q4_plan.hip). `k` counts LOGICAL rows (k = 2 * m.rows); ldm and m_batch count BYTES of the packed matrix; the other
+ * operands count their own elements (2 bytes for `x`, 4 for `scales` and `out`); *_addr16: the byte address of the view's first element modulo 16. */
+typedef struct wg_gemm_q4_query {
+    uint32_t k, outputs, n, mats;            /* contraction length in logical rows (2 * m.rows), outputs (m.cols), columns of x and out, matrices */
+    uint32_t group_rows;                     /* as passed: a positive multiple of 32, or any value >= k */
+    uint32_t x_bf16;                         /* x holds bfloat16 (the element name of the tag; no decision reads it) */
+    uint32_t ldm, lds, ldx, ldo;             /* leading dimensions of m (bytes), scales, x and out */
+    uint64_t m_batch, s_batch, x_batch, o_batch; /* matrix strides (m: bytes) */
+    uint32_t m_addr16, x_addr16, o_addr16;   /* byte address of the first element of m, x and out, modulo 16 (scales are read 4 bytes at a time: any view) */
+    uint32_t cus;                            /* compute units of the context's stream */
+} wg_gemm_q4_query;
+typedef enum wg_gemm_q4_leaf {
+    WG_GEMM_Q4_NOTHING = 0,      /* no output element: no launch, WG_OK */
+    WG_GEMM_Q4_UNSUPPORTED = 1,  /* no launch: the call returns `status` with `message` */
+    WG_GEMM_Q4_MFMA = 2,         /* the streaming kernel: 32 outputs per wave, 16-byte loads of 32 weights, v_mfma_f32_32x32x16_{f16,bf16} (gemm_q4_mfma_kernel) */
+    WG_GEMM_Q4_ANY = 3           /* element by element, a byte (two weights) per lane and step: any view (gemm_q4_any_kernel) */
+} wg_gemm_q4_leaf;
+typedef struct wg_gemm_q4_plan {
+    uint32_t leaf;                           /* wg_gemm_q4_leaf */
+    uint32_t step;                           /* logical rows of one step of the streaming kernel: 32. k % step == 0 is its condition, and step divides every cut */
+    uint32_t col_tiles, col_passes;          /* WG_GEMM_Q4_MFMA: 16-column accumulator tiles per wave (2 or 4: one or two 32 x 32 tiles) and passes over N -- pass i takes
+                                                columns [16 col_tiles i, 16 col_tiles (i + 1)) and streams the weights again; WG_GEMM_Q4_ANY: 0, 1 (a wave walks all columns) */
+    uint32_t out_per_block;                  /* outputs a workgroup owns: block b takes [b * out_per_block, (b + 1) * out_per_block) */
+    uint32_t nsplit, k_per_split;            /* cut of the contraction over grid.y in LOGICAL rows (1, k: none); no empty split, every boundary a multiple of 32 and,
+                                                where group_rows < k, of group_rows: a group is never cut */
+    uint32_t grid[3], block;                 /* the launch: grid = (output blocks, splits, mats * col_passes) */
+    uint64_t workspace_bytes;                /* f32 partials of a cut: mats * nsplit * n * outputs * 4 (the context's workspace), 0 without a cut */
+    int32_t status;                          /* WG_GEMM_Q4_NOTHING / _UNSUPPORTED */
+    char message[128];
+} wg_gemm_q4_plan;
+/* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the combine pass of a cut included. */
+int wg_debug_gemm_q4_plan(const wg_gemm_q4_query *query, wg_gemm_q4_plan *plan, char *tags, size_t cap);
 /* The same for the launcher of wg_gemv, wg_gemv_mixed and the fused wg_gemv_reduce (gemv_plan.hip): leaf, right-hand-side tile, cut of the contraction, grids and
  * workspace bytes as a pure function of the query. The query describes the call as the vec4 kernels get it (api.hip: the views as they are, or their staged copies);
  * sizes and strides count each operand's own elements. */
@@ -787,6 +820,54 @@ int wg_gemm_out32(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype in_dtype, float
 int wg_gemm_q8(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dtype x_dtype,
                wg_buf *out, wg_view_shape out_shape,             /* f32: outputs x N x mats */
                const wg_buf *m, wg_view_shape m_shape,           /* int8_t: k x outputs x mats, column-major */
+               const wg_buf *scales, wg_view_shape scales_shape, /* f32: ceil(k / group_rows) x outputs x mats */
+               const wg_buf *x, wg_view_shape x_shape);          /* x_dtype (WG_F16 or WG_BF16): k x N x mats */
+
+/*
+ * Extension: Gemm on packed 4-bit weights with group scales and 16-bit columns -- wg_gemv_q4's matrix and scales, byte for byte, against N columns of f16 / bf16
+ * activations on the matrix cores (the counterpart of wg_gemv_q4 as wg_gemm_q8 is of wg_gemv_q8). out = W^T x. `m` holds packed BYTES, k / 2 x outputs x mats,
+ * column-major: byte j of a column holds logical row 2 j in its LOW nibble and row 2 j + 1 in its HIGH nibble; a nibble n in 0 .. 15 stands for q = n - 8, all 16
+ * values are legal; W[r, c, z] = scales[r / G, c, z] * (float)q[r, c, z], G = group_rows. m_shape counts BYTES (rows, leading dimension, offset, matrix stride) and
+ * k = 2 * m.rows. `scales` holds f32, ceil(k / G) x outputs x mats; `x` holds x_dtype elements (WG_F16 or WG_BF16), k x N x mats; `out` holds f32, outputs x N x mats.
+ * The same `m` and `scales` buffers serve wg_gemv_q4. No alpha, no beta: `out` is overwritten. The bounds checks use 1 / 4 / 2 / 4 bytes per element of m / scales /
+ * x / out. wg_dtype has no 4-bit value and gets none.
+ *   variant       : WG_GEMM_TR and WG_GEMM_TR_FAST are the product above (_FAST is the same call). WG_GEMM and WG_GEMM_FAST return WG_ERR_UNSUPPORTED ("... wg_gemv_q8
+ *                   computes out = W v ..."), right behind the checks of the context, the buffers, x_dtype and the variant's range and BEFORE any dimension,
+ *                   group_rows or size is looked at, as wg_gemm_q8 and wg_gemv_q4 do: a mismatched or zero-sized call with these variants is UNSUPPORTED too.
+ *   x_dtype       : WG_F16 or WG_BF16. WG_F32 is WG_ERR_UNSUPPORTED (f32 vectors stay with wg_gemv_q4; the message names it); anything else WG_ERR_INVALID_ARG.
+ *   group_rows    : wg_gemv_q4's rule -- a positive multiple of 32, or any positive value >= k (one scale per output). Anything else is WG_ERR_INVALID_ARG.
+ *   DIM_MISMATCH  : x.rows != 2 * m.rows, out.rows != m.cols, out.cols != x.cols or unequal mats ("Gemm: dimension mismatch. (out [..], m1 [..]^T packed: k K,
+ *                   m2 [..])"); then `scales` of another shape than the one above ("Gemm: dimension mismatch. (m [..] packed: k K, group_rows G, scales [..],
+ *                   expected [..])").
+ * Everything else is wg_gemm_q8's contract, in its order, with its status codes: the NULL context ("Gemm: ctx is NULL"), NULL buffers, the unknown variant,
+ * zero-sized buffers / views skipped with WG_OK, views that exceed their buffer, WG_ERR_WORKSPACE when the partials of a cut contraction would have to grow the
+ * context's workspace inside a recording; mats * column passes > 65535 is WG_ERR_UNSUPPORTED.
+ * Arithmetic:
+ *   - q = n - 8 is formed exactly IN THE 16-BIT TYPE before any product (f16: (1024 + n) - 1032 and fma(1024 + 16 n, 1/16, -72), both exact; bf16: n as f32, minus
+ *     8, its high half). The -8 is never folded into a correction of the sum: a nibble of 8 is a true zero -- against a finite x it adds exactly nothing, against
+ *     Inf it gives NaN. `x` is read as the 16-bit value it is; every product is exact in f32 inside the MFMA;
+ *   - the scale enters per GROUP (the streaming kernel): d = the MFMA chain over the group's 32-row steps, started from zero, then acc = fmaf(scale, d, acc) in f32
+ *     on the vector ALU, groups ascending. A chain never holds rows of two groups (groups of 32 included). The unscaled d must be finite for a finite result. On
+ *     any other view (the element-by-element kernel): w = scale * q, acc = fmaf(w, (float)x, acc), even row first. Each of the k terms takes at most two f32
+ *     roundings either way;
+ *   - the f32 accumulator is stored as it is. Nothing is narrowed or flushed: subnormal scales and subnormal results are kept;
+ *   - Inf and NaN behave as in the f32 product of the dequantised matrix with `x` and reach exactly the outputs whose sums contain them; load slots past the end
+ *     of k and columns / outputs past the edge of a tile contribute nothing and are not stored;
+ *   - deterministic: no atomics; a cut contraction writes f32 partials that one pass adds in a fixed order -- two calls give identical bits.
+ * Which kernels (gemm_q4_plan.hip, wg_debug_gemm_q4_plan): the streaming kernel takes views where k % 32 == 0 -- the step is 32 logical rows; a lane's 16-byte load
+ * covers half of a 64-row double step and the halves of a wave exchange dwords, but a last double step of 32 rows is taken, so the condition is NOT k % 64 == 0 --,
+ * group_rows % 32 == 0 or group_rows >= k, and the first byte, leading dimension and matrix stride of `m` and the first element, leading dimension and matrix
+ * stride of `x` are multiples of 16 bytes; `scales` and `out` are reached one float at a time and may be any 4-byte-aligned view. A wave owns 32 outputs and 32 or
+ * 64 columns; N past 64 re-reads the weights once per pass of 64 columns. Every cut boundary is a multiple of 32 and, where group_rows < k, of group_rows. Every
+ * other view runs where it lies on the element-by-element kernel (a wave per output, a byte -- two weights -- per lane and step): correct, not fast, no padded copies.
+ *   ALIASED       : `out` shares a byte with the part of `m`, of `scales` or of `x` the call addresses -- on addresses, `m` in 1-byte and `x` in 2-byte units, so
+ *                   they may live in one buffer: touching is legal, one shared byte is refused. The read operands may overlap each other.
+ * Not included: out = W x, alpha / beta, zero points, f32 or int8 activations, the row-major and sharded surfaces.
+ * wg_debug_take_path: tags begin "gemm_q4/": "gemm_q4/mfma,f16,nt=2,ns=1" (x's element, 16-column tiles per wave, splits), "gemm_q4/combine,ns=8", "gemm_q4/any".
+ */
+int wg_gemm_q4(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dtype x_dtype,
+               wg_buf *out, wg_view_shape out_shape,             /* f32: outputs x N x mats */
+               const wg_buf *m, wg_view_shape m_shape,           /* packed bytes: k / 2 x outputs x mats, column-major */
                const wg_buf *scales, wg_view_shape scales_shape, /* f32: ceil(k / group_rows) x outputs x mats */
                const wg_buf *x, wg_view_shape x_shape);          /* x_dtype (WG_F16 or WG_BF16): k x N x mats */
 

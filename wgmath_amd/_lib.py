@@ -124,6 +124,24 @@ class GemmQ8PlanC(ctypes.Structure):
                 + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
 
 
+class GemmQ4QueryC(ctypes.Structure):
+    """wg_gemm_q4_query: everything wg_gemm_q4's choice of kernel, column tile, cut and grid depends on (wg_debug_gemm_q4_plan). `k` counts logical rows, `ldm` and
+    `m_batch` bytes."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("k", "outputs", "n", "mats", "group_rows", "x_bf16", "ldm", "lds", "ldx", "ldo")]
+                + [(n, ctypes.c_uint64) for n in ("m_batch", "s_batch", "x_batch", "o_batch")]
+                + [(n, ctypes.c_uint32) for n in ("m_addr16", "x_addr16", "o_addr16", "cus")])
+
+
+GEMM_Q4_LEAVES = ("nothing", "unsupported", "mfma", "any")  # wg_gemm_q4_leaf
+
+
+class GemmQ4PlanC(ctypes.Structure):
+    """wg_gemm_q4_plan: the leaf (index into GEMM_Q4_LEAVES) and what it is launched with; `step` and `k_per_split` count logical rows."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("leaf", "step", "col_tiles", "col_passes", "out_per_block", "nsplit", "k_per_split")]
+                + [("grid", ctypes.c_uint32 * 3), ("block", ctypes.c_uint32), ("workspace_bytes", ctypes.c_uint64)]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
+
+
 class GemvQueryC(ctypes.Structure):
     """wg_gemv_query: everything the Gemv launchers' choice of kernel, cut and grid depends on (wg_debug_gemv_plan, wg_debug_gemv_any_plan)."""
     _fields_ = ([(n, ctypes.c_uint32) for n in ("trans", "rows_out", "k", "nrhs", "nmats", "m_elem", "v_elem", "bf16", "gemm16", "ldm", "ldv", "ldo")]
@@ -239,6 +257,8 @@ def _load() -> ctypes.CDLL:
         "wg_debug_gemv_q4_plan": (ci, [ctypes.POINTER(GemvQ4QueryC), ctypes.POINTER(GemvQ4PlanC), cp, sz]),
         "wg_gemm_q8": (ci, [vp, ci, u32, ci, vp, S, vp, S, vp, S, vp, S]),
         "wg_debug_gemm_q8_plan": (ci, [ctypes.POINTER(GemmQ8QueryC), ctypes.POINTER(GemmQ8PlanC), cp, sz]),
+        "wg_gemm_q4": (ci, [vp, ci, u32, ci, vp, S, vp, S, vp, S, vp, S]),
+        "wg_debug_gemm_q4_plan": (ci, [ctypes.POINTER(GemmQ4QueryC), ctypes.POINTER(GemmQ4PlanC), cp, sz]),
         "wg_debug_gemv_plan": (ci, [ctypes.POINTER(GemvQueryC), ctypes.POINTER(GemvPlanC), cp, sz]),
         "wg_debug_gemv_any_plan": (ci, [ctypes.POINTER(GemvQueryC), ctypes.POINTER(GemvAnyPlanC), cp, sz]),
         "wg_gemm_out32": (ci, [vp, ci, ci, ctypes.c_float, ctypes.c_float, vp, S, vp, S, vp, S]),

@@ -7,6 +7,7 @@
 #include "gemv_q8_plan.hpp"
 #include "gemv_q4_plan.hpp"
 #include "gemm_q8_plan.hpp"
+#include "gemm_q4_plan.hpp"
 #include "gemv_plan.hpp"
 
 namespace {
@@ -568,6 +569,57 @@ int wg_gemm_q8(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dty
     const wg_gemm_q8_plan p = gemm_q8_plan(q);
     WG_HIP_TRY(hipSetDevice(ctx->device));
     return wgk_gemm_q8(ctx, p, x_dtype == WG_BF16, group_rows, mm.rows, mm.cols, o.cols, o.mats, O, o.stride, o.stride_mat, M, S, X);
+}
+
+// wg_gemm_q8 on wg_gemv_q4's packed matrix (include/wgebra_hip.h): wg_gemm_q8's checks in its order with its statuses; `m` counts bytes (two weights each), so the
+// contraction length is k = 2 m.rows and wg_gemv_q4's rule for group_rows applies; both refusals (f32 columns, out = W x) come before any dimension is looked at.
+// The kernels are the plan's (gemm_q4_plan.hip).
+int wg_gemm_q4(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dtype x_dtype, wg_buf *out, wg_view_shape out_shape, const wg_buf *m, wg_view_shape m_shape,
+               const wg_buf *scales, wg_view_shape scales_shape, const wg_buf *x, wg_view_shape x_shape) {
+    const wg_buf *bufs[4] = { out, m, scales, x };
+    if (int rc = check_common("Gemm", ctx, x_dtype, bufs, 4)) return rc;
+    if (x_dtype == WG_F32)
+        return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: wg_gemm_q4 takes f16 or bf16 columns (f32 activations stay with wg_gemv_q4, which never narrows them)");
+    if ((int)variant < 0 || (int)variant > 3) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: unknown variant %d", (int)variant);
+    if (variant != WG_GEMM_TR && variant != WG_GEMM_TR_FAST)
+        return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: wg_gemm_q4 computes out = W^T x only (WG_GEMM_TR); wg_gemv_q8 computes out = W v, on a layout with the groups along the outputs");
+    const View o = mk(out_shape), mm = mk(m_shape), ss = mk(scales_shape), xx = mk(x_shape);
+
+    const uint64_t k64 = 2ull * mm.rows;
+    if (k64 != xx.rows || mm.cols != o.rows || o.cols != xx.cols || o.mats != mm.mats || o.mats != xx.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemm: dimension mismatch. (out [%u,%u,%u], m1 [%u,%u,%u]^T packed: k %llu, m2 [%u,%u,%u])", o.rows, o.cols, o.mats, mm.rows,
+                            mm.cols, mm.mats, (unsigned long long)k64, xx.rows, xx.cols, xx.mats);
+    const uint32_t k = (uint32_t)k64;
+    if (group_rows == 0 || (group_rows % 32u != 0 && group_rows < k))
+        return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: group_rows %u is neither a positive multiple of 32 nor at least the %u logical rows of m", group_rows, k);
+    const uint32_t s_rows = k / group_rows + (k % group_rows != 0);
+    if (ss.rows != s_rows || ss.cols != mm.cols || ss.mats != mm.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemm: dimension mismatch. (m [%u,%u,%u] packed: k %u, group_rows %u, scales [%u,%u,%u], expected [%u,%u,%u])", mm.rows,
+                            mm.cols, mm.mats, k, group_rows, ss.rows, ss.cols, ss.mats, s_rows, mm.cols, mm.mats);
+    if (out->bytes == 0 || m->bytes == 0 || scales->bytes == 0 || x->bytes == 0) return WG_OK;
+    if (o.rows == 0 || o.cols == 0 || o.mats == 0) return WG_OK;
+
+    if (int rc = check_bounds("Gemm", "out", o, out, WG_F32)) return rc;
+    if (int rc = check_bounds_es("Gemm", "m", mm, m, 1)) return rc;
+    if (int rc = check_bounds("Gemm", "scales", ss, scales, WG_F32)) return rc;
+    if (int rc = check_bounds("Gemm", "x", xx, x, x_dtype)) return rc;
+    if (int rc = check_alias_f32_u8("Gemm", "out", o, out->ptr, "m", mm, m->ptr)) return rc;
+    if (int rc = check_alias("Gemm", WG_F32, "out", o, out->ptr, "scales", ss, scales->ptr)) return rc;
+    if (int rc = check_alias_f32_u16("Gemm", "out", o, out->ptr, "x", xx, x->ptr)) return rc;
+
+    const wgk_mat M = { (const char *)m->ptr + mm.offset, mm.stride, mm.stride_mat };
+    const wgk_mat S = { elem_ptr(scales, ss.offset, WG_F32), ss.stride, ss.stride_mat };
+    const wgk_mat X = { elem_ptr(x, xx.offset, x_dtype), xx.stride, xx.stride_mat };
+    float *O = (float *)elem_ptr(out, o.offset, WG_F32);
+    wg_gemm_q4_query q = {};
+    q.k = k; q.outputs = mm.cols; q.n = o.cols; q.mats = o.mats; q.group_rows = group_rows; q.x_bf16 = x_dtype == WG_BF16;
+    q.ldm = mm.stride; q.lds = ss.stride; q.ldx = xx.stride; q.ldo = o.stride;
+    q.m_batch = mm.stride_mat; q.s_batch = ss.stride_mat; q.x_batch = xx.stride_mat; q.o_batch = o.stride_mat;
+    q.m_addr16 = (uint32_t)((uintptr_t)M.ptr % 16u); q.x_addr16 = (uint32_t)((uintptr_t)X.ptr % 16u); q.o_addr16 = (uint32_t)((uintptr_t)O % 16u);
+    q.cus = (uint32_t)wg_ctx_cus(ctx);
+    const wg_gemm_q4_plan p = gemm_q4_plan(q);
+    WG_HIP_TRY(hipSetDevice(ctx->device));
+    return wgk_gemm_q4(ctx, p, x_dtype == WG_BF16, group_rows, k, mm.cols, o.cols, o.mats, O, o.stride, o.stride_mat, M, S, X);
 }
 
 int wg_reduce(wg_ctx *ctx, wg_reduce_op op, wg_dtype dtype, const wg_buf *value, wg_view_shape value_shape, wg_buf *result) {

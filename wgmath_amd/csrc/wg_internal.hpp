@@ -208,6 +208,10 @@ int wgk_gemv_q4(wg_ctx *ctx, const wg_gemv_q4_plan &p, uint32_t group_rows, uint
 // gemm_q8_plan.hip's; ld / batch strides count each operand's own elements.
 int wgk_gemm_q8(wg_ctx *ctx, const wg_gemm_q8_plan &p, bool bf16, uint32_t group_rows, uint32_t k, uint32_t outputs, uint32_t n, uint32_t nmats, float *out, uint32_t out_ld,
                 uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat x);
+// wg_gemm_q4 (gemm_q4.hip): out = W^T x on wg_gemv_q4's packed matrix (k / 2 bytes x outputs as stored; ld / batch in bytes) and scales, x holds f16 / bf16 (k x n), out
+// f32; k counts logical rows. Launch only: the plan is gemm_q4_plan.hip's.
+int wgk_gemm_q4(wg_ctx *ctx, const wg_gemm_q4_plan &p, bool bf16, uint32_t group_rows, uint32_t k, uint32_t outputs, uint32_t n, uint32_t nmats, float *out, uint32_t out_ld,
+                uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat x);
 // The Gemv launchers' query (gemv_plan.hpp: they ask gemv_plan and do what the plan says) of a call on these views in this context; m_dtype / v_dtype: the elements of
 // the matrix and of the vectors / the result; gemm16: wg_gemv on 16-bit elements, which the 16-bit Gemm kernels may take
 wg_gemv_query wgk_gemv_query(const wg_ctx *ctx, bool trans, wg_dtype m_dtype, wg_dtype v_dtype, bool gemm16, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats,

@@ -88,6 +88,18 @@ def _gemm_q8_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView,
     return wg_dtype(x._tensor.dtype)  # (float16 or bfloat16: every other element type is a TypeError there)
 
 
+def _gemm_q4_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView, x: GpuTensorView) -> int:
+    """The wg_dtype of `x` in a q4 Gemm: `m` uint8 (packed), `scales` and `out` float32, `x` float16 or bfloat16 -- anything else is a TypeError."""
+    if np.dtype(m._tensor.dtype) != np.dtype(np.uint8):
+        raise TypeError(f"q4 Gemm: `m` must be uint8 (two packed 4-bit weights per byte), got {m._tensor.dtype}")
+    for name, t in (("scales", scales), ("out", out)):
+        if np.dtype(t._tensor.dtype) != np.dtype(np.float32):
+            raise TypeError(f"q4 Gemm: `{name}` must be float32, got {t._tensor.dtype} (`m` carries the packed weights)")
+    if np.dtype(x._tensor.dtype) == np.dtype(np.float32):
+        raise TypeError("q4 Gemm: `x` must be float16 or bfloat16 (float32 activations are Gemv.dispatch_q4*)")
+    return wg_dtype(x._tensor.dtype)  # (float16 or bfloat16: every other element type is a TypeError there)
+
+
 def _q8_groups(rows: int, group_rows: int) -> int:
     group_rows = int(group_rows)
     if group_rows <= 0 or (group_rows % 16 and group_rows < rows):
@@ -296,6 +308,23 @@ class Gemm:
         if self.row_major:
             raise TypeError("Gemm.dispatch_q8*: the row-major operator surface has no q8 form")
         check(lib.wg_gemm_q8(pass_._ctx.handle, int(variant), int(group_rows), xd,
+                             out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
+                             scales.buffer()._h, scales.shape().to_c(), x.buffer()._h, x.shape().to_c()))
+
+    def dispatch_q4_tr(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, x, group_rows: int) -> None:
+        self.dispatch_q4_generic(device, shapes, pass_, out, m, scales, x, group_rows, GemmVariant.GemmTr)
+
+    def dispatch_q4_generic(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, x, group_rows: int,
+                            variant: GemmVariant = GemmVariant.GemmTr) -> None:
+        """Extension (`wg_gemm_q4`): `Gemv.dispatch_q4_tr`'s uint8 matrix of packed 4-bit weights and float32 group scales (`pack_q4` / `quantize_q4`'s layout,
+        k / 2 bytes x outputs) against float16 / bfloat16 columns `x` (k x N) with a float32 `out` (outputs x N) = W^T x on the matrix cores. A weight is unpacked
+        exactly (q = n - 8), nothing is narrowed, the scale enters per group in f32. Only the transposed variants exist (Gemm / GemmFast are refused by the
+        library). Column-major views only (the row-major surface has no q4 form)."""
+        out, m, scales, x = as_view(out, 3), as_view(m, 3), as_view(scales, 3), as_view(x, 3)
+        xd = _gemm_q4_dtypes(out, m, scales, x)
+        if self.row_major:
+            raise TypeError("Gemm.dispatch_q4*: the row-major operator surface has no q4 form")
+        check(lib.wg_gemm_q4(pass_._ctx.handle, int(variant), int(group_rows), xd,
                              out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
                              scales.buffer()._h, scales.shape().to_c(), x.buffer()._h, x.shape().to_c()))
 
