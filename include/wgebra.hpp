@@ -443,6 +443,18 @@ struct Gemm {
                         GpuTensorView<X> x, uint32_t group_rows) const {
         dispatch_q8_generic(d, s, p, out, m, scales, x, group_rows, GemmVariant::GemmTr);
     }
+    // extension (wg_gemm_q8a8): the same int8 weights and f32 group scales against int8 columns x (k x N) with f32 group scales of their own (x_scales:
+    // ceil(k / x_group_rows) x N x mats; QuantizeQ8 makes both), f32 result out (outputs x N) = W^T X on the i8 matrix cores. Only the transposed variants exist.
+    void dispatch_q8a8_generic(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<float> out, GpuTensorView<int8_t> m, GpuTensorView<float> scales,
+                               GpuTensorView<int8_t> x, GpuTensorView<float> x_scales, uint32_t group_rows, uint32_t x_group_rows,
+                               GemmVariant variant = GemmVariant::GemmTr) const {
+        check(wg_gemm_q8a8(pass.ctx(), (wg_gemm_variant)variant, group_rows, x_group_rows, out.buffer(), out.shape(), m.buffer(), m.shape(), scales.buffer(), scales.shape(),
+                           x.buffer(), x.shape(), x_scales.buffer(), x_scales.shape()));
+    }
+    void dispatch_q8a8_tr(const Device &d, const ViewShapeBuffers &s, ComputePass &p, GpuTensorView<float> out, GpuTensorView<int8_t> m, GpuTensorView<float> scales,
+                          GpuTensorView<int8_t> x, GpuTensorView<float> x_scales, uint32_t group_rows, uint32_t x_group_rows) const {
+        dispatch_q8a8_generic(d, s, p, out, m, scales, x, x_scales, group_rows, x_group_rows, GemmVariant::GemmTr);
+    }
     // extension (wg_gemm_q4): Gemv::dispatch_q4_tr's packed 4-bit weights -- m holds BYTES, k / 2 x outputs; byte j of a column carries logical row 2 j in its low and
     // row 2 j + 1 in its high nibble, q = n - 8 -- and f32 group scales (ceil(k / group_rows) x outputs x mats) against 16-bit columns x (X = _Float16 / bf16, k x N)
     // with an f32 result out (outputs x N) = W^T x on the matrix cores. Only the transposed variants exist (the library refuses Gemm / GemmFast, and X = float).
@@ -567,6 +579,17 @@ struct CopyView {
     template <typename T>
     void dispatch(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<T> dst, GpuTensorView<T> src) const {
         check(wg_copy_view(pass.ctx(), dtype_of<T>::value, dst.buffer(), dst.shape(), src.buffer(), src.shape()));
+    }
+};
+
+// extension (wg_quantize_q8): the device-side quantiser of the q8 family -- int8 q and f32 group scales (ceil(rows / group_rows) x cols x mats) from a source of
+// X = float / _Float16 / bf16, the rule of the Python helper quantize_q8 on the source widened exactly to f32. Serves activations and weights alike.
+struct QuantizeQ8 {
+    static QuantizeQ8 from_device(const Device &) { return {}; }
+    template <typename X>
+    void dispatch(const Device &, const ViewShapeBuffers &, ComputePass &pass, GpuTensorView<int8_t> q, GpuTensorView<float> scales, GpuTensorView<X> src,
+                  uint32_t group_rows) const {
+        check(wg_quantize_q8(pass.ctx(), dtype_of<X>::value, group_rows, q.buffer(), q.shape(), scales.buffer(), scales.shape(), src.buffer(), src.shape()));
     }
 };
 

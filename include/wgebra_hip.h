@@ -58,6 +58,7 @@ extern "C" {
                                     wg_gemm_q8 with wg_debug_gemm_q8_plan and its two structs (added symbols; wg_dtype is unchanged);
                                     wg_gemv_q4 with wg_debug_gemv_q4_plan and its two structs (added symbols; wg_dtype is unchanged);
                                     wg_gemm_q4 with wg_debug_gemm_q4_plan and its two structs (added symbols; wg_dtype is unchanged);
+                                    wg_gemm_q8a8 with wg_debug_gemm_q8a8_plan, wg_quantize_q8 with wg_debug_quantize_q8_plan, and their two structs each (added symbols; wg_dtype is unchanged);
                                     wg_debug_gemv_plan and wg_debug_gemv_any_plan with wg_gemv_query and their plan structs (added diagnostic symbols);
                                     4: wg_gemm_sharded_panels (ragged N-panels), wg_ctx_mem_info, geometry ops 15-18; 3: the SDMA rect-copy exchange engine (gather mode 1, wg_comm_copy_engine, wg_gemm_sharded's peer_out) is gone;
                                     wg_comm_reported_size, wg_debug_*; non-vec4 views compute staged; async time-outs surface in wg_ctx_sync */
@@ -453,6 +454,60 @@ typedef struct wg_gemm_q8_plan {
 } wg_gemm_q8_plan;
 /* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the combine pass of a cut included. */
 int wg_debug_gemm_q8_plan(const wg_gemm_q8_query *query, wg_gemm_q8_plan *plan, char *tags, size_t cap);
+/* The same for wg_gemm_q8a8's launcher (gemm_q8a8_plan.hip): wg_gemm_q8_query's fields plus the activations' group size and the view of their scales. Sizes and
+ * strides count each operand's own elements (1 byte for `m` and `x`, 4 for `scales`, `x_scales` and `out`); *_addr16: the byte address of the view's first element
+ * modulo 16. */
+typedef struct wg_gemm_q8a8_query {
+    uint32_t k, outputs, n, mats;            /* contraction length (m.rows), outputs (m.cols), columns of x and out, matrices */
+    uint32_t group_rows, x_group_rows;       /* as passed: each a positive multiple of 16, or any value >= k; where both are below k one divides the other */
+    uint32_t ldm, lds, ldx, ldxs, ldo;       /* leading dimensions of m, scales, x, x_scales and out */
+    uint64_t m_batch, s_batch, x_batch, xs_batch, o_batch; /* matrix strides */
+    uint32_t m_addr16, x_addr16, o_addr16;   /* byte address of the first element of m, x and out, modulo 16 (the scales are read 4 bytes at a time: any view) */
+    uint32_t cus;                            /* compute units of the context's stream */
+} wg_gemm_q8a8_query;
+typedef enum wg_gemm_q8a8_leaf {
+    WG_GEMM_Q8A8_NOTHING = 0,      /* no output element: no launch, WG_OK */
+    WG_GEMM_Q8A8_UNSUPPORTED = 1,  /* no launch: the call returns `status` with `message` */
+    WG_GEMM_Q8A8_MFMA = 2,         /* the streaming kernel: 32 outputs per wave, 16-byte loads of both operands, v_mfma_i32_32x32x32_i8 (gemm_q8a8_mfma_kernel) */
+    WG_GEMM_Q8A8_ANY = 3           /* element by element: any view (gemm_q8a8_any_kernel) */
+} wg_gemm_q8a8_leaf;
+typedef struct wg_gemm_q8a8_plan {
+    uint32_t leaf;                           /* wg_gemm_q8a8_leaf */
+    uint32_t col_tiles, col_passes;          /* WG_GEMM_Q8A8_MFMA: 16-column accumulator tiles per wave (2 or 4: one or two 32 x 32 tiles) and passes over N -- pass i takes
+                                                columns [16 col_tiles i, 16 col_tiles (i + 1)) and streams the weights again; WG_GEMM_Q8A8_ANY: 0, 1 (a wave walks all columns) */
+    uint32_t out_per_block;                  /* outputs a workgroup owns: block b takes [b * out_per_block, (b + 1) * out_per_block) */
+    uint32_t nsplit, k_per_split;            /* cut of the contraction over grid.y (1, k: none); no empty split; every boundary is a CHAIN boundary: a multiple of 32, of
+                                                whichever group sizes are below k and, where neither is, of 1024 */
+    uint32_t grid[3], block;                 /* the launch: grid = (output blocks, splits, mats * col_passes) */
+    uint64_t workspace_bytes;                /* f32 partials of a cut: mats * nsplit * n * outputs * 4 (the context's workspace), 0 without a cut */
+    int32_t status;                          /* WG_GEMM_Q8A8_NOTHING / _UNSUPPORTED */
+    char message[128];
+} wg_gemm_q8a8_plan;
+/* plan: the plan of `query`. tags (may be NULL): the launch log such a call leaves (the format of wg_debug_take_path), the combine pass of a cut included. */
+int wg_debug_gemm_q8a8_plan(const wg_gemm_q8a8_query *query, wg_gemm_q8a8_plan *plan, char *tags, size_t cap);
+/* The choice of wg_quantize_q8's launcher (quantize_q8.hip) as a pure function of the query: leaf, block and grid. Strides count each operand's own elements;
+ * *_addr16: the byte address of the view's first element modulo 16; src_elem: bytes per source element (4 or 2). */
+typedef struct wg_quantize_q8_query {
+    uint32_t rows, cols, mats, group_rows, src_elem;
+    uint32_t ldq, ldsrc;
+    uint64_t q_batch, src_batch;
+    uint32_t q_addr16, src_addr16;
+} wg_quantize_q8_query;
+typedef enum wg_quantize_q8_leaf {
+    WG_QUANTIZE_Q8_NOTHING = 0,      /* no element: no launch, WG_OK */
+    WG_QUANTIZE_Q8_UNSUPPORTED = 1,  /* no launch: the call returns `status` with `message` */
+    WG_QUANTIZE_Q8_VEC = 2,          /* a lane per 16 rows: 16-byte loads and one 16-byte store, the max over the group_rows / 16 lanes of a group by cross-lane exchange */
+    WG_QUANTIZE_Q8_ANY = 3           /* a wave or a workgroup per (group, column) in two sweeps, element by element: any view */
+} wg_quantize_q8_leaf;
+typedef struct wg_quantize_q8_plan {
+    uint32_t leaf;                           /* wg_quantize_q8_leaf */
+    uint32_t group_lanes;                    /* VEC: lanes that share a group (group_rows / 16: a power of two, 2 .. 64) */
+    uint32_t blocks_per_col;                 /* grid.x = blocks_per_col * cols: VEC -- workgroups of 256 lanes per column; ANY -- groups per column */
+    uint32_t grid[3], block;                 /* the launch: grid = (blocks_per_col * cols, 1, mats); ANY: 64 threads up to 1024 rows per group, else 256 */
+    int32_t status;
+    char message[128];
+} wg_quantize_q8_plan;
+int wg_debug_quantize_q8_plan(const wg_quantize_q8_query *query, wg_quantize_q8_plan *plan);
 /* The same for wg_gemm_q4's launcher (gemm_q4_plan.hip). `k` counts LOGICAL rows (k = 2 * m.rows); ldm and m_batch count BYTES of the packed matrix; the other
  * operands count their own elements (2 bytes for `x`, 4 for `scales` and `out`); *_addr16: the byte address of the view's first element modulo 16. */
 typedef struct wg_gemm_q4_query {
@@ -814,7 +869,7 @@ int wg_gemm_out32(wg_ctx *ctx, wg_gemm_variant variant, wg_dtype in_dtype, float
  * the element-by-element kernel -- correct, not fast, no padded copies.
  *   ALIASED       : `out` shares a byte with the part of `m`, of `scales` or of `x` the call addresses -- on addresses, `m` in 1-byte and `x` in 2-byte units, so
  *                   they may live in one buffer: touching is legal, one shared byte is refused. The read operands may overlap each other.
- * Not included: out = W x, alpha / beta, f32 or int8 activations, the row-major and sharded surfaces.
+ * Not included: out = W x, alpha / beta, f32 activations, the row-major and sharded surfaces. int8 activations are wg_gemm_q8a8's.
  * wg_debug_take_path: tags begin "gemm_q8/": "gemm_q8/mfma,f16,nt=4,ns=8" (x's element, 16-column tiles per wave, splits), "gemm_q8/combine,ns=8", "gemm_q8/any".
  */
 int wg_gemm_q8(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dtype x_dtype,
@@ -862,7 +917,7 @@ int wg_gemm_q8(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dty
  * other view runs where it lies on the element-by-element kernel (a wave per output, a byte -- two weights -- per lane and step): correct, not fast, no padded copies.
  *   ALIASED       : `out` shares a byte with the part of `m`, of `scales` or of `x` the call addresses -- on addresses, `m` in 1-byte and `x` in 2-byte units, so
  *                   they may live in one buffer: touching is legal, one shared byte is refused. The read operands may overlap each other.
- * Not included: out = W x, alpha / beta, zero points, f32 or int8 activations, the row-major and sharded surfaces.
+ * Not included: out = W x, alpha / beta, zero points, f32 or int8 activations (int8 against 8-bit weights: wg_gemm_q8a8), the row-major and sharded surfaces.
  * wg_debug_take_path: tags begin "gemm_q4/": "gemm_q4/mfma,f16,nt=2,ns=1" (x's element, 16-column tiles per wave, splits), "gemm_q4/combine,ns=8", "gemm_q4/any".
  */
 int wg_gemm_q4(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dtype x_dtype,
@@ -870,6 +925,72 @@ int wg_gemm_q4(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, wg_dty
                const wg_buf *m, wg_view_shape m_shape,           /* packed bytes: k / 2 x outputs x mats, column-major */
                const wg_buf *scales, wg_view_shape scales_shape, /* f32: ceil(k / group_rows) x outputs x mats */
                const wg_buf *x, wg_view_shape x_shape);          /* x_dtype (WG_F16 or WG_BF16): k x N x mats */
+
+/*
+ * Extension: Gemm on 8-bit weights AND 8-bit activations, both with f32 group scales (W8A8: per-channel weights x per-token activations, or Q8_0 x Q8_1-style groups
+ * on both sides), on the i8 matrix cores. out = W^T X with W[r, c, z] = scales[r / G, c, z] * m[r, c, z] and X[r, j, z] = x_scales[r / Gx, j, z] * x[r, j, z],
+ * G = group_rows, Gx = x_group_rows. `m` and `scales` are wg_gemv_q8's and wg_gemm_q8's buffers, byte for byte; `x` holds int8_t, k x N x mats, column-major;
+ * `x_scales` f32, ceil(k / Gx) x N x mats; `out` f32, outputs x N x mats. All 256 int8 values are legal on both sides. No alpha, no beta: `out` is overwritten. The
+ * bounds checks use 1 / 4 / 1 / 4 / 4 bytes per element of m / scales / x / x_scales / out. wg_quantize_q8 below makes `x` and `x_scales` on the device.
+ *   variant       : WG_GEMM_TR and WG_GEMM_TR_FAST are the product above (_FAST is the same call). WG_GEMM and WG_GEMM_FAST return WG_ERR_UNSUPPORTED ("... wg_gemv_q8
+ *                   computes out = W v ..."), right behind the checks of the context, the buffers and the variant's range and BEFORE any dimension, group size or
+ *                   size is looked at, as wg_gemm_q8 does.
+ *   group sizes   : group_rows and x_group_rows are each a positive multiple of 16, or any positive value >= k (one scale per output / per column). Where both are
+ *                   below k one must divide the other. Anything else is WG_ERR_INVALID_ARG.
+ *   DIM_MISMATCH  : the Gemm check with wg_gemm_q8's message; then `scales` of another shape than the one above ("Gemm: dimension mismatch. (m [..], group_rows G,
+ *                   scales [..], expected [..])"); then `x_scales` ("Gemm: dimension mismatch. (x [..], x_group_rows Gx, x_scales [..], expected [..])").
+ * Everything else is wg_gemm_q8's contract, in its order, with its status codes: the NULL context ("Gemm: ctx is NULL"), NULL buffers, the unknown variant,
+ * zero-sized buffers / views skipped with WG_OK, views that exceed their buffer, WG_ERR_WORKSPACE when the partials of a cut contraction would have to grow the
+ * context's workspace inside a recording; mats * column passes > 65535 is WG_ERR_UNSUPPORTED.
+ * Arithmetic -- ONE definition for every kernel; the bits of an uncut call do not depend on which kernel ran:
+ *   - the contraction is divided into CHAINS: a chain ends at every boundary of a weight group and of an activation group and, inside the finer of the two groups,
+ *     every 1024 rows counted from that group's start;
+ *   - d = the chain's integer sum of m * x in int32, exact: |d| <= 1024 * 128 * 128 = 2^24, so (float)d is exact too (without the cap an int32 chain overflows
+ *     from 2^17 rows on and (float)d rounds from 1025 rows on: the cap is part of the contract);
+ *   - u = x_scale * (float)d, one f32 multiply; acc = fmaf(w_scale, u, acc), chains ascending (a tiny weight scale never enters an intermediate product);
+ *   - the f32 accumulator is stored as it is. Nothing is narrowed or flushed: subnormal scales and results are kept;
+ *   - non-finite scales behave as these two f32 operations say (0 * Inf is NaN) and reach exactly the outputs whose chains hold them;
+ *   - deterministic: no atomics; a cut contraction writes f32 partials [z][split][n][outputs] that one pass adds in gemm_q8's fixed order (wave w adds splits w,
+ *     w + 4, ... ascending, then the four are added ascending) -- two calls give identical bits. A cut changes the bits (its partial sums start from zero).
+ * Which kernels (gemm_q8a8_plan.hip, wg_debug_gemm_q8a8_plan): the streaming kernel takes views where k % 32 == 0, each group size % 32 == 0 or >= k, and the first
+ * element, leading dimension and matrix stride of `m` and of `x` are multiples of 16 bytes; the scales and `out` are reached one float at a time and may be any
+ * 4-byte-aligned view. Both operands go into v_mfma_i32_32x32x32_i8 exactly as loaded: no conversion. A wave owns 32 outputs and 32 or 64 columns; N past 64 re-reads
+ * the weights once per pass of 64 columns. Every cut boundary is a chain boundary. Every other view runs where it lies on the element-by-element kernel: the same
+ * chains, the same two f32 operations, no padded copies.
+ *   ALIASED       : `out` shares a byte with the part of `m`, `scales`, `x` or `x_scales` the call addresses -- on addresses, `m` and `x` in 1-byte units: touching is
+ *                   legal, one shared byte is refused. The read operands may overlap each other.
+ * Not included: out = W x, alpha / beta, 4-bit weights against int8 activations, zero points, the row-major and sharded surfaces.
+ * wg_debug_take_path: tags begin "gemm_q8a8/": "gemm_q8a8/mfma,nt=2,ns=1" (16-column tiles per wave, splits), "gemm_q8a8/combine,ns=8", "gemm_q8a8/any".
+ */
+int wg_gemm_q8a8(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, uint32_t x_group_rows,
+                 wg_buf *out, wg_view_shape out_shape,                  /* f32: outputs x N x mats */
+                 const wg_buf *m, wg_view_shape m_shape,                /* int8_t: k x outputs x mats, column-major */
+                 const wg_buf *scales, wg_view_shape scales_shape,      /* f32: ceil(k / group_rows) x outputs x mats */
+                 const wg_buf *x, wg_view_shape x_shape,                /* int8_t: k x N x mats, column-major */
+                 const wg_buf *x_scales, wg_view_shape x_scales_shape); /* f32: ceil(k / x_group_rows) x N x mats */
+
+/*
+ * Extension: the device-side quantiser of the q8 family -- activations (k x N) and weights (k x outputs) alike. The rule is the Python helper quantize_q8's on the
+ * source widened exactly to f32: per group of group_rows consecutive rows of a column (a partial last group) s = fl32(max|x| / 127) and
+ * q = clip(rint(fl32(x / s)), -127, 127) -- a true IEEE division per element (not a multiply by a reciprocal: the two differ at ties), rounding ties to even, the
+ * clamp before the integer conversion; -128 is never produced. s == 0 (an all-zero group, or one whose max / 127 rounds to zero) gives q = 0. A group whose
+ * max|x| is not finite (it holds a NaN or an Inf) gets s = NaN and q = 0 throughout.
+ * `q` holds int8_t, rows x cols x mats; `scales` f32, ceil(rows / group_rows) x cols x mats; `src` holds src_dtype elements (WG_F32, WG_F16, WG_BF16) in q's shape.
+ *   group_rows    : a positive multiple of 16, or any positive value >= rows (one scale per column). Anything else is WG_ERR_INVALID_ARG.
+ *   DIM_MISMATCH  : "Quantize: dimension mismatch. (q [..], src [..])", then "Quantize: dimension mismatch. (q [..], group_rows G, scales [..], expected [..])".
+ * NULL context / buffers and an unknown src_dtype are WG_ERR_INVALID_ARG; zero-sized buffers / views are skipped with WG_OK; a view that exceeds its buffer is
+ * WG_ERR_OUT_OF_BOUNDS (1 / 4 / src bytes per element of q / scales / src); more than 2^31 - 1 workgroups or 65535 matrices is WG_ERR_UNSUPPORTED.
+ *   ALIASED       : `q` or `scales` shares a byte with the addressed part of `src`, or with each other (on addresses, in 1-byte units).
+ * It needs no workspace and works inside a recording. Deterministic.
+ * Which kernels (quantize_q8.hip, wg_debug_quantize_q8_plan): group_rows in 32, 64, .. 1024 (a power of two), rows % 16 == 0 and first element, leading dimension
+ * and matrix stride of `q` and `src` multiples of 16 bytes: a lane per 16 rows, 16-byte accesses, the group's max by cross-lane exchange. Everything else, one scale
+ * per column included: a wave (groups up to 1024 rows) or a workgroup per (group, column), two sweeps, where it lies.
+ * wg_debug_take_path: "quantize_q8/vec,f16", "quantize_q8/any,bf16" (the source's element).
+ */
+int wg_quantize_q8(wg_ctx *ctx, wg_dtype src_dtype, uint32_t group_rows,
+                   wg_buf *q, wg_view_shape q_shape,            /* int8_t: rows x cols x mats */
+                   wg_buf *scales, wg_view_shape scales_shape,  /* f32: ceil(rows / group_rows) x cols x mats */
+                   const wg_buf *src, wg_view_shape src_shape); /* src_dtype (WG_F32, WG_F16, WG_BF16): rows x cols x mats */
 
 /*
  * ROW_MAJOR operator surface. Replaces composing the reference's shaders with

@@ -8,7 +8,7 @@ from ._lib import (LIB_PATH, AliasedOperands, DimensionMismatch, NoDevice, Preco
 from .wgcore import (BufferUsages, CommandBuffer, CommandEncoder, ComputePass, Device, GpuCube, GpuInstance,  # noqa: F401
                      GpuBuffer, GpuMatrix, GpuScalar, GpuTensor, GpuTensorView, GpuTimestamps, ComputePassTimestampWrites, GpuVector, Queue, TensorBuilder,
                      ViewShape, ViewShapeBuffers, as_view, bfloat16, from_bfloat16, to_bfloat16)
-from .wgebra import (Axpy, CopyView, Gemm, GemmVariant, Gemv, GemvVariant, OpAssign, OpAssignVariant, Reduce, ReduceOp,  # noqa: F401
+from .wgebra import (Axpy, CopyView, Gemm, GemmVariant, Gemv, GemvVariant, OpAssign, OpAssignVariant, QuantizeQ8, Reduce, ReduceOp,  # noqa: F401
                      dequantize_q4, dequantize_q8, gemv_reduce, pack_q4, quantize_q4, quantize_q8, row_major_shader_defs, unpack_q4)
 from .sharded import Comm, GatherMode, MShardPlan, ShardedGemm, new_unique_id  # noqa: F401,E402
 from . import geometry  # noqa: F401,E402

@@ -124,6 +124,40 @@ class GemmQ8PlanC(ctypes.Structure):
                 + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
 
 
+class GemmQ8A8QueryC(ctypes.Structure):
+    """wg_gemm_q8a8_query: wg_gemm_q8_query's fields plus the activations' group size and the view of their scales (wg_debug_gemm_q8a8_plan)."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("k", "outputs", "n", "mats", "group_rows", "x_group_rows", "ldm", "lds", "ldx", "ldxs", "ldo")]
+                + [(n, ctypes.c_uint64) for n in ("m_batch", "s_batch", "x_batch", "xs_batch", "o_batch")]
+                + [(n, ctypes.c_uint32) for n in ("m_addr16", "x_addr16", "o_addr16", "cus")])
+
+
+GEMM_Q8A8_LEAVES = ("nothing", "unsupported", "mfma", "any")  # wg_gemm_q8a8_leaf
+
+
+class GemmQ8A8PlanC(ctypes.Structure):
+    """wg_gemm_q8a8_plan: the leaf (index into GEMM_Q8A8_LEAVES) and what it is launched with."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("leaf", "col_tiles", "col_passes", "out_per_block", "nsplit", "k_per_split")]
+                + [("grid", ctypes.c_uint32 * 3), ("block", ctypes.c_uint32), ("workspace_bytes", ctypes.c_uint64)]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
+
+
+class QuantizeQ8QueryC(ctypes.Structure):
+    """wg_quantize_q8_query: everything wg_quantize_q8's choice of kernel and grid depends on (wg_debug_quantize_q8_plan)."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("rows", "cols", "mats", "group_rows", "src_elem", "ldq", "ldsrc")]
+                + [(n, ctypes.c_uint64) for n in ("q_batch", "src_batch")]
+                + [(n, ctypes.c_uint32) for n in ("q_addr16", "src_addr16")])
+
+
+QUANTIZE_Q8_LEAVES = ("nothing", "unsupported", "vec", "any")  # wg_quantize_q8_leaf
+
+
+class QuantizeQ8PlanC(ctypes.Structure):
+    """wg_quantize_q8_plan: the leaf (index into QUANTIZE_Q8_LEAVES), the lanes of a group, and the launch."""
+    _fields_ = ([(n, ctypes.c_uint32) for n in ("leaf", "group_lanes", "blocks_per_col")]
+                + [("grid", ctypes.c_uint32 * 3), ("block", ctypes.c_uint32)]
+                + [("status", ctypes.c_int32), ("message", ctypes.c_char * 128)])
+
+
 class GemmQ4QueryC(ctypes.Structure):
     """wg_gemm_q4_query: everything wg_gemm_q4's choice of kernel, column tile, cut and grid depends on (wg_debug_gemm_q4_plan). `k` counts logical rows, `ldm` and
     `m_batch` bytes."""
@@ -259,6 +293,10 @@ def _load() -> ctypes.CDLL:
         "wg_debug_gemm_q8_plan": (ci, [ctypes.POINTER(GemmQ8QueryC), ctypes.POINTER(GemmQ8PlanC), cp, sz]),
         "wg_gemm_q4": (ci, [vp, ci, u32, ci, vp, S, vp, S, vp, S, vp, S]),
         "wg_debug_gemm_q4_plan": (ci, [ctypes.POINTER(GemmQ4QueryC), ctypes.POINTER(GemmQ4PlanC), cp, sz]),
+        "wg_gemm_q8a8": (ci, [vp, ci, u32, u32, vp, S, vp, S, vp, S, vp, S, vp, S]),
+        "wg_debug_gemm_q8a8_plan": (ci, [ctypes.POINTER(GemmQ8A8QueryC), ctypes.POINTER(GemmQ8A8PlanC), cp, sz]),
+        "wg_quantize_q8": (ci, [vp, ci, u32, vp, S, vp, S, vp, S]),
+        "wg_debug_quantize_q8_plan": (ci, [ctypes.POINTER(QuantizeQ8QueryC), ctypes.POINTER(QuantizeQ8PlanC)]),
         "wg_debug_gemv_plan": (ci, [ctypes.POINTER(GemvQueryC), ctypes.POINTER(GemvPlanC), cp, sz]),
         "wg_debug_gemv_any_plan": (ci, [ctypes.POINTER(GemvQueryC), ctypes.POINTER(GemvAnyPlanC), cp, sz]),
         "wg_gemm_out32": (ci, [vp, ci, ci, ctypes.c_float, ctypes.c_float, vp, S, vp, S, vp, S]),

@@ -8,6 +8,7 @@
 #include "gemv_q4_plan.hpp"
 #include "gemm_q8_plan.hpp"
 #include "gemm_q4_plan.hpp"
+#include "gemm_q8a8_plan.hpp"
 #include "gemv_plan.hpp"
 
 namespace {
@@ -895,6 +896,131 @@ int wg_gemv_rm(wg_ctx *ctx, wg_gemv_variant variant, wg_dtype dtype, wg_buf *out
         return wg_gemm_rm(ctx, tr ? WG_GEMM_TR : WG_GEMM, dtype, out, os, m, ms, v, vs);
     }
     return wg_gemv(ctx, tr ? WG_GEMV : WG_GEMV_TR, dtype, out, out_shape, m, relabel(m_shape), v, v_shape);
+}
+
+// wg_gemm_q8 with int8 columns and their f32 group scales (include/wgebra_hip.h): wg_gemm_q8's checks in its order with its statuses, the refusal of out = W x before
+// any dimension is looked at; both group sizes behind the Gemm dimension check, then the shape of `scales`, then of `x_scales`; bounds with 1 / 4 / 1 / 4 / 4 bytes per
+// element of m / scales / x / x_scales / out; `out` against `m` and `x` in 1-byte units. The kernels are the plan's (gemm_q8a8_plan.hip).
+int wg_gemm_q8a8(wg_ctx *ctx, wg_gemm_variant variant, uint32_t group_rows, uint32_t x_group_rows, wg_buf *out, wg_view_shape out_shape, const wg_buf *m, wg_view_shape m_shape,
+                 const wg_buf *scales, wg_view_shape scales_shape, const wg_buf *x, wg_view_shape x_shape, const wg_buf *x_scales, wg_view_shape x_scales_shape) {
+    const wg_buf *bufs[5] = { out, m, scales, x, x_scales };
+    if (int rc = check_common("Gemm", ctx, WG_F32, bufs, 5)) return rc;
+    if ((int)variant < 0 || (int)variant > 3) return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: unknown variant %d", (int)variant);
+    if (variant != WG_GEMM_TR && variant != WG_GEMM_TR_FAST)
+        return wg_set_error(WG_ERR_UNSUPPORTED, "Gemm: wg_gemm_q8a8 computes out = W^T x only (WG_GEMM_TR); wg_gemv_q8 computes out = W v, whose scales cannot leave the contraction");
+    const View o = mk(out_shape), mm = mk(m_shape), ss = mk(scales_shape), xx = mk(x_shape), xs = mk(x_scales_shape);
+
+    if (mm.rows != xx.rows || mm.cols != o.rows || o.cols != xx.cols || o.mats != mm.mats || o.mats != xx.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemm: dimension mismatch. (out [%u,%u,%u], m1 [%u,%u,%u]^T, m2 [%u,%u,%u])", o.rows, o.cols, o.mats, mm.rows, mm.cols,
+                            mm.mats, xx.rows, xx.cols, xx.mats);
+    const uint32_t k = mm.rows;
+    if (group_rows == 0 || (group_rows % 16u != 0 && group_rows < k))
+        return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: group_rows %u is neither a positive multiple of 16 nor at least the %u rows of m", group_rows, k);
+    if (x_group_rows == 0 || (x_group_rows % 16u != 0 && x_group_rows < k))
+        return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: x_group_rows %u is neither a positive multiple of 16 nor at least the %u rows of x", x_group_rows, k);
+    if (group_rows < k && x_group_rows < k && group_rows % x_group_rows != 0 && x_group_rows % group_rows != 0)
+        return wg_set_error(WG_ERR_INVALID_ARG, "Gemm: of group_rows %u and x_group_rows %u, both below the %u rows, neither divides the other", group_rows, x_group_rows, k);
+    const uint32_t s_rows = k / group_rows + (k % group_rows != 0);
+    if (ss.rows != s_rows || ss.cols != mm.cols || ss.mats != mm.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemm: dimension mismatch. (m [%u,%u,%u], group_rows %u, scales [%u,%u,%u], expected [%u,%u,%u])", mm.rows, mm.cols, mm.mats,
+                            group_rows, ss.rows, ss.cols, ss.mats, s_rows, mm.cols, mm.mats);
+    const uint32_t xs_rows = k / x_group_rows + (k % x_group_rows != 0);
+    if (xs.rows != xs_rows || xs.cols != xx.cols || xs.mats != xx.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Gemm: dimension mismatch. (x [%u,%u,%u], x_group_rows %u, x_scales [%u,%u,%u], expected [%u,%u,%u])", xx.rows, xx.cols, xx.mats,
+                            x_group_rows, xs.rows, xs.cols, xs.mats, xs_rows, xx.cols, xx.mats);
+    if (out->bytes == 0 || m->bytes == 0 || scales->bytes == 0 || x->bytes == 0 || x_scales->bytes == 0) return WG_OK;
+    if (o.rows == 0 || o.cols == 0 || o.mats == 0) return WG_OK;
+
+    if (int rc = check_bounds("Gemm", "out", o, out, WG_F32)) return rc;
+    if (int rc = check_bounds_es("Gemm", "m", mm, m, 1)) return rc;
+    if (int rc = check_bounds("Gemm", "scales", ss, scales, WG_F32)) return rc;
+    if (int rc = check_bounds_es("Gemm", "x", xx, x, 1)) return rc;
+    if (int rc = check_bounds("Gemm", "x_scales", xs, x_scales, WG_F32)) return rc;
+    if (int rc = check_alias_f32_u8("Gemm", "out", o, out->ptr, "m", mm, m->ptr)) return rc;
+    if (int rc = check_alias("Gemm", WG_F32, "out", o, out->ptr, "scales", ss, scales->ptr)) return rc;
+    if (int rc = check_alias_f32_u8("Gemm", "out", o, out->ptr, "x", xx, x->ptr)) return rc;
+    if (int rc = check_alias("Gemm", WG_F32, "out", o, out->ptr, "x_scales", xs, x_scales->ptr)) return rc;
+
+    const wgk_mat M = { (const char *)m->ptr + mm.offset, mm.stride, mm.stride_mat };
+    const wgk_mat S = { elem_ptr(scales, ss.offset, WG_F32), ss.stride, ss.stride_mat };
+    const wgk_mat X = { (const char *)x->ptr + xx.offset, xx.stride, xx.stride_mat };
+    const wgk_mat XS = { elem_ptr(x_scales, xs.offset, WG_F32), xs.stride, xs.stride_mat };
+    float *O = (float *)elem_ptr(out, o.offset, WG_F32);
+    wg_gemm_q8a8_query q = {};
+    q.k = k; q.outputs = mm.cols; q.n = o.cols; q.mats = o.mats; q.group_rows = group_rows; q.x_group_rows = x_group_rows;
+    q.ldm = mm.stride; q.lds = ss.stride; q.ldx = xx.stride; q.ldxs = xs.stride; q.ldo = o.stride;
+    q.m_batch = mm.stride_mat; q.s_batch = ss.stride_mat; q.x_batch = xx.stride_mat; q.xs_batch = xs.stride_mat; q.o_batch = o.stride_mat;
+    q.m_addr16 = (uint32_t)((uintptr_t)M.ptr % 16u); q.x_addr16 = (uint32_t)((uintptr_t)X.ptr % 16u); q.o_addr16 = (uint32_t)((uintptr_t)O % 16u);
+    q.cus = (uint32_t)wg_ctx_cus(ctx);
+    const wg_gemm_q8a8_plan p = gemm_q8a8_plan(q);
+    WG_HIP_TRY(hipSetDevice(ctx->device));
+    return wgk_gemm_q8a8(ctx, p, group_rows, x_group_rows, k, mm.cols, o.cols, o.mats, O, o.stride, o.stride_mat, M, S, X, XS);
+}
+
+namespace {
+// Two views of any element sizes (1, 2 or 4 bytes), both in 1-byte units (views_overlap.hpp's scaling, for either side): a view with rows, stride and stride_mat
+// multiplied by its element size and its offset folded into the byte base has the same footprint as a view of 1-byte elements. A scaled field that leaves 32 bits
+// leaves the intervals: disjoint intervals are disjoint footprints, anything else is refused as "may overlap".
+bool bytes_view(const View &v, const void *base, uint32_t es, wg_view_shape &out, uint64_t &byte_base) {
+    const uint64_t rows = (uint64_t)es * v.rows, stride = v.cols > 1 ? (uint64_t)es * v.stride : rows, stride_mat = v.mats > 1 ? (uint64_t)es * v.stride_mat : 0;
+    byte_base = (uint64_t)(uintptr_t)base + (uint64_t)es * v.offset;
+    if (rows > 0xffffffffull || stride > 0xffffffffull || stride_mat > 0xffffffffull) return false;
+    out = wg_view_shape{ { (uint32_t)rows, v.cols, v.mats }, (uint32_t)stride, (uint32_t)stride_mat, 0 };
+    return true;
+}
+int check_alias_bytes(const char *op, const char *wname, const View &w, const void *base_w, uint32_t wes, const char *rname, const View &r, const void *base_r, uint32_t res) {
+    if (extent(w) == 0 || extent(r) == 0) return WG_OK;
+    wg_view_shape a, b;
+    uint64_t ba, bb;
+    const bool oka = bytes_view(w, base_w, wes, a, ba), okb = bytes_view(r, base_r, res, b, bb);
+    int exact = 1;
+    if (oka && okb) {
+        if (!wg_views_overlap(a, ba, b, bb, 1, &exact)) return WG_OK;
+        return aliased(op, wname, rname, exact);
+    }
+    typedef unsigned __int128 u128;
+    const u128 lo_a = ba, hi_a = lo_a + (u128)wes * (extent(w) - w.offset), lo_b = bb, hi_b = lo_b + (u128)res * (extent(r) - r.offset);
+    if (hi_a <= lo_b || hi_b <= lo_a) return WG_OK;
+    return aliased(op, wname, rname, 0);
+}
+} // namespace
+
+// The device-side quantiser (include/wgebra_hip.h): q and scales from src. The checks: context, dtype and buffers; q against src, group_rows, the scales' shape; empty
+// operands skipped; bounds with 1 / 4 / src bytes per element; q and scales against src and against each other, on addresses. The kernels: quantize_q8.hip.
+int wg_quantize_q8(wg_ctx *ctx, wg_dtype src_dtype, uint32_t group_rows, wg_buf *q, wg_view_shape q_shape, wg_buf *scales, wg_view_shape scales_shape, const wg_buf *src,
+                   wg_view_shape src_shape) {
+    const wg_buf *bufs[3] = { q, scales, src };
+    if (int rc = check_common("Quantize", ctx, src_dtype, bufs, 3)) return rc;
+    const View qq = mk(q_shape), ss = mk(scales_shape), sv = mk(src_shape);
+    if (qq.rows != sv.rows || qq.cols != sv.cols || qq.mats != sv.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Quantize: dimension mismatch. (q [%u,%u,%u], src [%u,%u,%u])", qq.rows, qq.cols, qq.mats, sv.rows, sv.cols, sv.mats);
+    if (group_rows == 0 || (group_rows % 16u != 0 && group_rows < qq.rows))
+        return wg_set_error(WG_ERR_INVALID_ARG, "Quantize: group_rows %u is neither a positive multiple of 16 nor at least the %u rows of src", group_rows, qq.rows);
+    const uint32_t s_rows = qq.rows / group_rows + (qq.rows % group_rows != 0);
+    if (ss.rows != s_rows || ss.cols != qq.cols || ss.mats != qq.mats)
+        return wg_set_error(WG_ERR_DIM_MISMATCH, "Quantize: dimension mismatch. (q [%u,%u,%u], group_rows %u, scales [%u,%u,%u], expected [%u,%u,%u])", qq.rows, qq.cols, qq.mats,
+                            group_rows, ss.rows, ss.cols, ss.mats, s_rows, qq.cols, qq.mats);
+    if (q->bytes == 0 || scales->bytes == 0 || src->bytes == 0) return WG_OK;
+    if (qq.rows == 0 || qq.cols == 0 || qq.mats == 0) return WG_OK;
+
+    const uint32_t es = (uint32_t)wg_dtype_size(src_dtype);
+    if (int rc = check_bounds_es("Quantize", "q", qq, q, 1)) return rc;
+    if (int rc = check_bounds("Quantize", "scales", ss, scales, WG_F32)) return rc;
+    if (int rc = check_bounds("Quantize", "src", sv, src, src_dtype)) return rc;
+    if (int rc = check_alias_bytes("Quantize", "q", qq, q->ptr, 1, "src", sv, src->ptr, es)) return rc;
+    if (int rc = check_alias_bytes("Quantize", "scales", ss, scales->ptr, 4, "src", sv, src->ptr, es)) return rc;
+    if (int rc = check_alias_bytes("Quantize", "q", qq, q->ptr, 1, "scales", ss, scales->ptr, 4)) return rc;
+
+    int8_t *Q = (int8_t *)q->ptr + qq.offset;
+    float *S = (float *)elem_ptr(scales, ss.offset, WG_F32);
+    const wgk_mat SRC = { elem_ptr(src, sv.offset, src_dtype), sv.stride, sv.stride_mat };
+    wg_quantize_q8_query qu = {};
+    qu.rows = qq.rows; qu.cols = qq.cols; qu.mats = qq.mats; qu.group_rows = group_rows; qu.src_elem = es;
+    qu.ldq = qq.stride; qu.ldsrc = sv.stride; qu.q_batch = qq.stride_mat; qu.src_batch = sv.stride_mat;
+    qu.q_addr16 = (uint32_t)((uintptr_t)Q % 16u); qu.src_addr16 = (uint32_t)((uintptr_t)SRC.ptr % 16u);
+    const wg_quantize_q8_plan p = quantize_q8_plan(qu);
+    WG_HIP_TRY(hipSetDevice(ctx->device));
+    return wgk_quantize_q8(ctx, p, src_dtype, group_rows, qq.rows, qq.cols, qq.mats, Q, qq.stride, qq.stride_mat, S, ss.stride, ss.stride_mat, SRC);
 }
 
 } // extern "C"

@@ -212,6 +212,14 @@ int wgk_gemm_q8(wg_ctx *ctx, const wg_gemm_q8_plan &p, bool bf16, uint32_t group
 // f32; k counts logical rows. Launch only: the plan is gemm_q4_plan.hip's.
 int wgk_gemm_q4(wg_ctx *ctx, const wg_gemm_q4_plan &p, bool bf16, uint32_t group_rows, uint32_t k, uint32_t outputs, uint32_t n, uint32_t nmats, float *out, uint32_t out_ld,
                 uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat x);
+// wg_gemm_q8a8 (gemm_q8a8.hip): out = W^T X on the same int8 matrix and scales against int8 columns x (k x n) with their f32 group scales xs, out f32. Launch only:
+// the plan is gemm_q8a8_plan.hip's; ld / batch strides count each operand's own elements.
+int wgk_gemm_q8a8(wg_ctx *ctx, const wg_gemm_q8a8_plan &p, uint32_t group_rows, uint32_t x_group_rows, uint32_t k, uint32_t outputs, uint32_t n, uint32_t nmats, float *out,
+                  uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat x, wgk_mat xs);
+// wg_quantize_q8 (quantize_q8.hip): q / scales from src (src_dtype elements). quantize_q8_plan is the launcher's choice, a pure function; the launcher logs its tag.
+wg_quantize_q8_plan quantize_q8_plan(const wg_quantize_q8_query &q);
+int wgk_quantize_q8(wg_ctx *ctx, const wg_quantize_q8_plan &p, wg_dtype src_dtype, uint32_t group_rows, uint32_t rows, uint32_t cols, uint32_t nmats, int8_t *q, uint32_t q_ld,
+                    uint64_t q_batch, float *s, uint32_t s_ld, uint64_t s_batch, wgk_mat src);
 // The Gemv launchers' query (gemv_plan.hpp: they ask gemv_plan and do what the plan says) of a call on these views in this context; m_dtype / v_dtype: the elements of
 // the matrix and of the vectors / the result; gemm16: wg_gemv on 16-bit elements, which the 16-bit Gemm kernels may take
 wg_gemv_query wgk_gemv_query(const wg_ctx *ctx, bool trans, wg_dtype m_dtype, wg_dtype v_dtype, bool gemm16, uint32_t rows_out, uint32_t k, uint32_t nrhs, uint32_t nmats,

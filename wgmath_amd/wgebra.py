@@ -88,6 +88,16 @@ def _gemm_q8_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView,
     return wg_dtype(x._tensor.dtype)  # (float16 or bfloat16: every other element type is a TypeError there)
 
 
+def _gemm_q8a8_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView, x: GpuTensorView, x_scales: GpuTensorView) -> None:
+    """The element types of a q8a8 Gemm: `m` and `x` int8, `scales`, `x_scales` and `out` float32 -- anything else is a TypeError."""
+    for name, t in (("m", m), ("x", x)):
+        if np.dtype(t._tensor.dtype) != np.dtype(np.int8):
+            raise TypeError(f"q8a8 Gemm: `{name}` must be int8, got {t._tensor.dtype}" + (" (float16 / bfloat16 activations are Gemm.dispatch_q8*)" if name == "x" else ""))
+    for name, t in (("scales", scales), ("x_scales", x_scales), ("out", out)):
+        if np.dtype(t._tensor.dtype) != np.dtype(np.float32):
+            raise TypeError(f"q8a8 Gemm: `{name}` must be float32, got {t._tensor.dtype} (`m` and `x` carry the int8 values)")
+
+
 def _gemm_q4_dtypes(out: GpuTensorView, m: GpuTensorView, scales: GpuTensorView, x: GpuTensorView) -> int:
     """The wg_dtype of `x` in a q4 Gemm: `m` uint8 (packed), `scales` and `out` float32, `x` float16 or bfloat16 -- anything else is a TypeError."""
     if np.dtype(m._tensor.dtype) != np.dtype(np.uint8):
@@ -311,6 +321,23 @@ class Gemm:
                              out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(),
                              scales.buffer()._h, scales.shape().to_c(), x.buffer()._h, x.shape().to_c()))
 
+    def dispatch_q8a8_tr(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, x, x_scales, group_rows: int, x_group_rows: int) -> None:
+        self.dispatch_q8a8_generic(device, shapes, pass_, out, m, scales, x, x_scales, group_rows, x_group_rows, GemmVariant.GemmTr)
+
+    def dispatch_q8a8_generic(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, x, x_scales, group_rows: int, x_group_rows: int,
+                              variant: GemmVariant = GemmVariant.GemmTr) -> None:
+        """Extension (`wg_gemm_q8a8`): `dispatch_q8_tr`'s int8 matrix and float32 group scales (k x outputs) against int8 columns `x` (k x N) with float32 group
+        scales of their own (`x_scales`: ceil(k / x_group_rows) x N; `QuantizeQ8` makes both on the device), float32 `out` (outputs x N) = W^T X on the i8 matrix
+        cores. Integer chains of at most 1024 rows are exact; the two scales enter per chain in f32. Only the transposed variants exist (Gemm / GemmFast are
+        refused by the library). Column-major views only (the row-major surface has no q8a8 form)."""
+        out, m, scales, x, x_scales = as_view(out, 3), as_view(m, 3), as_view(scales, 3), as_view(x, 3), as_view(x_scales, 3)
+        _gemm_q8a8_dtypes(out, m, scales, x, x_scales)
+        if self.row_major:
+            raise TypeError("Gemm.dispatch_q8a8*: the row-major operator surface has no q8a8 form")
+        check(lib.wg_gemm_q8a8(pass_._ctx.handle, int(variant), int(group_rows), int(x_group_rows),
+                               out.buffer()._h, out.shape().to_c(), m.buffer()._h, m.shape().to_c(), scales.buffer()._h, scales.shape().to_c(),
+                               x.buffer()._h, x.shape().to_c(), x_scales.buffer()._h, x_scales.shape().to_c()))
+
     def dispatch_q4_tr(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, out, m, scales, x, group_rows: int) -> None:
         self.dispatch_q4_generic(device, shapes, pass_, out, m, scales, x, group_rows, GemmVariant.GemmTr)
 
@@ -507,3 +534,26 @@ class CopyView:
         d, s_ = as_view(dst, 3), as_view(src, 3)
         dt = _common_dtype(d, s_)
         check(lib.wg_copy_view(pass_._ctx.handle, dt, d.buffer()._h, d.shape().to_c(), s_.buffer()._h, s_.shape().to_c()))
+
+
+class QuantizeQ8:
+    """Extension (`wg_quantize_q8`): `dispatch(device, shapes, pass, q, scales, src, group_rows)`: the device-side `quantize_q8` -- int8 `q` and float32 `scales`
+    (ceil(rows / group_rows) x cols) from a float32 / float16 / bfloat16 `src`, the NumPy helper's rule on the source widened exactly to float32 (a true division
+    per element, ties to even, clamped to +-127; a group holding a NaN or an Inf gets the scale NaN and q = 0). Serves activations and weights alike."""
+
+    def __init__(self, device=None):
+        self.device = device
+
+    @staticmethod
+    def from_device(device) -> "QuantizeQ8":
+        return QuantizeQ8(device)
+
+    def dispatch(self, device, shapes: ViewShapeBuffers, pass_: ComputePass, q, scales, src, group_rows: int) -> None:
+        q, scales, src = as_view(q, 3), as_view(scales, 3), as_view(src, 3)
+        if np.dtype(q._tensor.dtype) != np.dtype(np.int8):
+            raise TypeError(f"QuantizeQ8: `q` must be int8, got {q._tensor.dtype}")
+        if np.dtype(scales._tensor.dtype) != np.dtype(np.float32):
+            raise TypeError(f"QuantizeQ8: `scales` must be float32, got {scales._tensor.dtype}")
+        sd = wg_dtype(src._tensor.dtype)  # (float32, float16 or bfloat16: every other element type is a TypeError there)
+        check(lib.wg_quantize_q8(pass_._ctx.handle, sd, int(group_rows), q.buffer()._h, q.shape().to_c(), scales.buffer()._h, scales.shape().to_c(),
+                                 src.buffer()._h, src.shape().to_c()))
