@@ -43,6 +43,41 @@ CASES = (
        _case("any_x", 64, 9, 3, 32, tag="gemm_q4/any", x=(1, 0))])
 CASE_IDS = [c["name"] for c in CASES]
 EXACT_CASES = CASES  # every case: _q4.exact_scale_exp(k) gives 2^-2 .. 2^2 up to k = 16384 and 2^0 .. 2^1 for the cut one
+WHOLE = 1 << 30  # a group size >= every k here: one scale per output
+
+
+def _cut(name, k, outputs, n, G, Z=1, nt=2, ns=2, **views):
+    return _case(name, k, outputs, n, G, Z, tag="gemm_q4/mfma,{dt},nt=%d,ns=%d" % (nt, ns), **views)
+
+
+# The cut contraction (k over grid.y, f32 partials [z][split][n][outputs] in the workspace, a combine pass): tests/_gemm_q8.py's rows on the packed matrix. A lane's
+# 16-byte load covers half a double step of 64 rows: a split of 17 steps (544 rows) ENDS on half a double step in the middle of k, and the next one begins at byte
+# offset 16 mod 32. tests/test_gemm_q4_plan_host.py pins ns and the rows per split of every row, and that some split starts on an odd step.
+CUT_CASES = [
+    _cut("cut_odd_steps", 1088, 16, 16, 32),                     # 2 x 544: 17 steps per split; half a double step mid-k; the second split starts on an odd step
+    _cut("cut_short_last", 1600, 33, 20, 32, ns=3),              # 544, 544, 512: a shorter last split; a second wave with one live output
+    _cut("cut_g96_partial", 1120, 33, 20, 96),                   # 576, 544: 6 groups per split (no power of two); the last split ends inside a group of 64 rows
+    _cut("cut_g64_views", 1152, 17, 9, 64, Z=2, m=(32, 16, 48), x=(8, 8), o=(1, 3, 5)),  # two_mats' strides and a gap between the matrices of `out`: z > 0
+    _cut("cut_per_column", 1088, 33, 20, WHOLE),                 # one scale per output under a cut (groups_per_split 0)
+    _cut("cut_passes", 1088, 130, 65, 32, nt=4),                 # T = 2 under a cut; a pass of one column; a second workgroup; the combine's third block has 2 live outputs
+    _cut("cut_passes_mats", 2048, 65, 130, 128, Z=3, nt=4, ns=4),  # blockIdx.z = z * passes + pass with both above 1
+    _cut("cut_ns5", 2560, 16, 16, 32, ns=5),                     # the combine: wave 0 adds two splits, waves 1 .. 3 one each
+    _cut("cut_ns29", 14848, 33, 20, WHOLE, ns=29),               # wave 0 on the 8-wide loop, waves 1 .. 3 on the tail alone
+    _cut("cut_ns32", 16384, 70, 3, 128, ns=32),                  # every wave exactly one wide trip, no tail; the combine's second block
+    _cut("cut_ns33", 16896, 16, 16, 32, ns=33),                  # one tail element behind a wide trip, on wave 0 only
+    _cut("cut_ns36", 18432, 16, 16, 32, ns=36),                  # one tail element on every wave
+    _cut("cut_masked", 4096, 130, 130, 32, Z=2, nt=4, ns=8),     # 12 workgroups: ns 8 on 256 CUs, 6 on 16, 3 on 8
+]
+CUT_IDS = [c["name"] for c in CUT_CASES]
+CUT_LANE_MAP = _cut("cut_lane_map", 1088, 32, 32, 32)
+DIRTY = _case("dirty", 4096, 256, 192, 32, tag="gemm_q4/mfma,{dt},nt=4,ns=8")  # the call that fills the workspace with NaN partials before a cut case runs
+out_view = G8.out_view
+
+
+def by_name(name):
+    return [c for c in CASES + CUT_CASES if c["name"] == name][0]
+
+
 LANE_MAP = _case("lane_map", 64, 32, 32, 32)
 IDENTITY = _case("identity", 2 * STEP, 32, 2 * STEP, 32, tag="gemm_q4/mfma,{dt},nt=4,ns=1")  # N = k, x the identity: out[o, r] = s q[r, o]
 
@@ -84,7 +119,7 @@ def model32(q, s, x, G, order="sequential"):
 def query_kw(c, dt, cus=256):
     """The wg_gemm_q4_query a call on the case's views fills (buffers are 256-byte aligned: a view's address modulo 16 is its offset's)."""
     k, outs, n, Z, G = c["k"], c["outputs"], c["n"], c["Z"], c["G"]
-    (moff, mpad, gap), (xoff, xpad), (ooff, opad) = c["m"], c["x"], c["o"]
+    (moff, mpad, gap), (xoff, xpad), (ooff, opad, ogap) = c["m"], c["x"], out_view(c)
     ldm, ldx, ldo, lds = k // 2 + mpad, k + xpad, outs + opad, _q4.n_groups(k, G) + 1
     return dict(k=k, outputs=outs, n=n, mats=Z, group_rows=G, x_bf16=int(dt == "bf16"), ldm=ldm, lds=lds, ldx=ldx, ldo=ldo, m_batch=ldm * outs + gap, s_batch=lds * outs + 2,
-                x_batch=ldx * n, o_batch=ldo * n, m_addr16=moff % 16, x_addr16=2 * xoff % 16, o_addr16=4 * ooff % 16, cus=cus)
+                x_batch=ldx * n, o_batch=ldo * n + ogap, m_addr16=moff % 16, x_addr16=2 * xoff % 16, o_addr16=4 * ooff % 16, cus=cus)

@@ -46,6 +46,54 @@ CASES = (
 CASE_IDS = [c["name"] for c in CASES]
 EXACT_CASES = [c for c in CASES if c["k"] <= 2048]  # the exact operands need k <= 2048
 
+WHOLE = 1 << 30  # a group size >= every k here: one scale per output
+
+
+def _cut(name, k, outputs, n, G, Z=1, nt=2, ns=2, **views):
+    return _case(name, k, outputs, n, G, Z, tag="gemm_q8/mfma,{dt},nt=%d,ns=%d" % (nt, ns), **views)
+
+
+# The cut contraction (k over grid.y, f32 partials [z][split][n][outputs] in the workspace, a combine pass): the smallest shapes that reach each line. The floor is 512
+# rows per split, so k >= 1024; 4 x 256 CUs against one or a few workgroups always want more splits than k / 512 allows: ns = k // 512 and the rows per split are
+# ceil(k / ns) rounded up to the group (to 32 where the group is the whole column). tests/test_gemm_q8_plan_host.py pins ns and the rows per split of every row.
+CUT_CASES = [
+    _cut("cut_odd_steps", 1088, 16, 16, 32),                     # 2 x 544: 17 steps per split, the second split starts on an odd step
+    _cut("cut_short_last", 1600, 33, 20, 32, ns=3),              # 544, 544, 512: a shorter last split; a second wave with one live output
+    _cut("cut_g96_partial", 1120, 33, 20, 96),                   # 576, 544: 6 groups per split (no power of two); the last split ends inside a group of 64 rows
+    _cut("cut_g64_views", 1152, 17, 9, 64, Z=2, m=(32, 16, 48), x=(8, 8), o=(1, 3, 5)),  # two_mats' strides and a gap between the matrices of `out`: z > 0
+    _cut("cut_per_column", 1088, 33, 20, WHOLE),                 # one scale per output under a cut (groups_per_split 0)
+    _cut("cut_passes", 1088, 130, 65, 32, nt=4),                 # T = 2 under a cut; a pass of one column; a second workgroup; the combine's third block has 2 live outputs
+    _cut("cut_passes_mats", 2048, 65, 130, 128, Z=3, nt=4, ns=4),  # blockIdx.z = z * passes + pass with both above 1
+    _cut("cut_ns5", 2560, 16, 16, 32, ns=5),                     # the combine: wave 0 adds two splits, waves 1 .. 3 one each
+    _cut("cut_ns29", 14848, 33, 20, WHOLE, ns=29),               # wave 0 on the 8-wide loop, waves 1 .. 3 on the tail alone
+    _cut("cut_ns32", 16384, 70, 3, 128, ns=32),                  # every wave exactly one wide trip, no tail; the combine's second block
+    _cut("cut_ns33", 16896, 16, 16, 32, ns=33),                  # one tail element behind a wide trip, on wave 0 only
+    _cut("cut_ns36", 18432, 16, 16, 32, ns=36),                  # one tail element on every wave
+    _cut("cut_masked", 4096, 130, 130, 32, Z=2, nt=4, ns=8),     # 12 workgroups: ns 8 on 256 CUs, 6 on 16, 3 on 8
+]
+CUT_IDS = [c["name"] for c in CUT_CASES]
+CUT_LANE_MAP = _cut("cut_lane_map", 1088, 32, 32, 32)
+DIRTY = _case("dirty", 4096, 256, 192, 32, tag="gemm_q8/mfma,{dt},nt=4,ns=8")  # the call that fills the workspace with NaN partials before a cut case runs
+
+
+def by_name(name):
+    return [c for c in CASES + CUT_CASES if c["name"] == name][0]
+
+
+def out_view(c):
+    """(element offset, leading-dimension padding, gap between matrices) of `out`: a case's o is (offset, padding) or all three."""
+    return tuple(c["o"]) + (0,) * (3 - len(c["o"]))
+
+
+def cut_exact_inputs(c, dt, salt=1):
+    """Exact operands for a cut case of any length: exact_inputs up to k = 2048; beyond, its narrower variant -- q over the full range with -128 and 127 planted, x in
+    {-1, 0, 1}, scales 2^0 or 2^1: 2 * 128 k < 2^24 up to k = 65535. The tests assert _q8.exactness_condition on what they draw."""
+    if c["k"] <= 2048:
+        return exact_inputs(c, dt, salt=salt)
+    q, s, _ = _q8.exact_inputs(q8case(c, dt), (0, 1), salt)
+    x = _q8.rng_of(c["name"] + dt, salt + 50).integers(-1, 2, (c["k"], c["n"], c["Z"])).astype(np.float32)
+    return q, s, x
+
 
 def q8case(c, suffix=""):
     """The case in tests/_q8.py's form: (name, GemvTr, rows, cols, right-hand sides, matrices, group_rows)."""
@@ -97,10 +145,10 @@ def truth64(q, s, x, G):
 def query_kw(c, dt, cus=256):
     """The wg_gemm_q8_query a call on the case's views fills (buffers are 256-byte aligned: a view's address modulo 16 is its offset's)."""
     k, outs, n, Z, G = c["k"], c["outputs"], c["n"], c["Z"], c["G"]
-    (moff, mpad, gap), (xoff, xpad), (ooff, opad) = c["m"], c["x"], c["o"]
+    (moff, mpad, gap), (xoff, xpad), (ooff, opad, ogap) = c["m"], c["x"], out_view(c)
     ldm, ldx, ldo, lds = k + mpad, k + xpad, outs + opad, _q8.n_groups(k, G) + 1
     return dict(k=k, outputs=outs, n=n, mats=Z, group_rows=G, x_bf16=int(dt == "bf16"), ldm=ldm, lds=lds, ldx=ldx, ldo=ldo, m_batch=ldm * outs + gap, s_batch=lds * outs + 2,
-                x_batch=ldx * n, o_batch=ldo * n, m_addr16=moff % 16, x_addr16=2 * xoff % 16, o_addr16=4 * ooff % 16, cus=cus)
+                x_batch=ldx * n, o_batch=ldo * n + ogap, m_addr16=moff % 16, x_addr16=2 * xoff % 16, o_addr16=4 * ooff % 16, cus=cus)
 
 
 # ---- the float32 model -------------------------------------------------------------------------------------------------------------------------------
@@ -121,16 +169,18 @@ def model32(q, s, x, G, order="sequential"):
     k, outs, Z = q.shape
     n = x.shape[1]
     out = np.zeros((outs, n, Z), np.float32)
-    for z in range(Z):
-        P = q[:, :, None, z].astype(np.float32) * x[:, None, :, z].astype(np.float32)  # [k, outs, n], exact
-        assert np.array_equal(P.astype(np.float64), q[:, :, None, z].astype(np.float64) * x[:, None, :, z].astype(np.float64))
+    ob = max(1, min(outs, (1 << 23) // max(k * n, 1)))  # outputs per block (they do not interact): the products of a block stay near 8 M elements
+    for z, o0 in ((z, o0) for z in range(Z) for o0 in range(0, outs, ob)):
+        qb, sb = q[:, o0:o0 + ob, None, z], s[:, o0:o0 + ob, z]
+        P = qb.astype(np.float32) * x[:, None, :, z].astype(np.float32)  # [k, block, n], exact
+        assert np.array_equal(P.astype(np.float64), qb.astype(np.float64) * x[:, None, :, z].astype(np.float64))
         parts = []
-        acc = np.zeros((outs, n), np.float32)
+        acc = np.zeros(P.shape[1:], np.float32)
         for g in range(_q8.n_groups(k, G)):
             d = _chain(P[g * G:(g + 1) * G], order)
             if order == "sequential":
-                acc = U.fmaf_f32(s[g, :, z][:, None], d, acc)
+                acc = U.fmaf_f32(sb[g][:, None], d, acc)
             else:
-                parts.append(U.fmaf_f32(s[g, :, z][:, None], d, np.float32(0)))
-        out[:, :, z] = acc if order == "sequential" else _chain(np.stack(parts), order)
+                parts.append(U.fmaf_f32(sb[g][:, None], d, np.float32(0)))
+        out[o0:o0 + ob, :, z] = acc if order == "sequential" else _chain(np.stack(parts), order)
     return out

@@ -56,8 +56,44 @@ CASE_IDS = [c["name"] for c in CASES]
 ALL_MIN = ("chain_cap", "cut")  # the cases whose operands are all -128
 
 
+def _cut(name, k, outputs, n, G, Gx=None, Z=1, nt=2, ns=2, **views):
+    return _case(name, k, outputs, n, G, Gx, Z, tag="gemm_q8a8/mfma,nt=%d,ns=%d" % (nt, ns), **views)
+
+
+# The cut contraction (k over grid.y, f32 partials [z][split][n][outputs] in the workspace, a combine pass): tests/_gemm_q8.py's rows with Gx = G, and four rows on the
+# chains under a cut. The cut unit is the coarser group, or 1024 rows where neither side has groups (k = 1024 ns there). tests/test_gemm_q8a8_plan_host.py pins ns and
+# the rows per split of every row.
+CUT_CASES = [
+    _cut("cut_odd_steps", 1088, 16, 16, 32),                     # 2 x 544: 17 steps per split, the second split starts on an odd step
+    _cut("cut_short_last", 1600, 33, 20, 32, ns=3),              # 544, 544, 512: a shorter last split; a second wave with one live output
+    _cut("cut_g96_partial", 1120, 33, 20, 96),                   # 576, 544: 6 groups per split (no power of two); the last split ends inside a group of 64 rows
+    _cut("cut_g64_views", 1152, 17, 9, 64, Z=2, m=(32, 16, 48), x=(16, 16), o=(1, 3, 5)),  # two_mats' strides and a gap between the matrices of `out`: z > 0
+    _cut("cut_per_column", 2048, 33, 20, WHOLE, WHOLE),          # one scale per output and per column under a cut: 2 x 1024
+    _cut("cut_passes", 1088, 130, 65, 32, nt=4),                 # T = 2 under a cut; a pass of one column; a second workgroup; the combine's third block has 2 live outputs
+    _cut("cut_passes_mats", 2048, 65, 130, 128, Z=3, nt=4, ns=4),  # blockIdx.z = z * passes + pass with both above 1
+    _cut("cut_ns5", 2560, 16, 16, 32, ns=5),                     # the combine: wave 0 adds two splits, waves 1 .. 3 one each
+    _cut("cut_ns29", 29696, 33, 20, WHOLE, WHOLE, ns=29),        # wave 0 on the 8-wide loop, waves 1 .. 3 on the tail alone
+    _cut("cut_ns32", 16384, 70, 3, 128, ns=32),                  # every wave exactly one wide trip, no tail; the combine's second block
+    _cut("cut_ns33", 16896, 16, 16, 32, ns=33),                  # one tail element behind a wide trip, on wave 0 only
+    _cut("cut_ns36", 18432, 16, 16, 32, ns=36),                  # one tail element on every wave
+    _cut("cut_masked", 4096, 130, 130, 32, Z=2, nt=4, ns=8),     # 12 workgroups: ns 8 on 256 CUs, 6 on 16, 3 on 8
+    _cut("cut_w1536", 3072, 33, 20, 1536, WHOLE),                # 2 x 1536: chains of 1024 + 512 inside each split
+    _cut("cut_g64_128", 1152, 33, 20, 64, 128),                  # the unit is the coarser group: 640 + 512; G != Gx under a cut
+    _cut("cut_x2048", 4096, 16, 65, WHOLE, 2048, nt=4),          # only the activation side grouped: the chain cap restarts at the split (2 x (1024 + 1024)); 2 passes
+    _cut("cut_g32_whole", 1088, 17, 9, 32, WHOLE, Z=2),          # weights grouped, activations per column
+]
+CUT_IDS = [c["name"] for c in CUT_CASES]
+CUT_LANE_MAP = _cut("cut_lane_map", 1088, 32, 32, 32)
+DIRTY = _case("dirty", 4096, 256, 192, 32, tag="gemm_q8a8/mfma,nt=4,ns=8")  # the call that fills the workspace with NaN partials before a cut case runs
+
+
+def out_view(c):
+    """(element offset, leading-dimension padding, gap between matrices) of `out`: a case's o is (offset, padding) or all three."""
+    return tuple(c["o"]) + (0,) * (3 - len(c["o"]))
+
+
 def by_name(name):
-    return [c for c in CASES if c["name"] == name][0]
+    return [c for c in CASES + CUT_CASES if c["name"] == name][0]
 
 
 def n_groups(k, G):
@@ -91,6 +127,14 @@ def pow2_inputs(c, w_exps=(-2, 2), x_exps=(-2, 2), salt=1):
     return q, s, x, xs
 
 
+def cut_pow2_inputs(c, salt=1):
+    """pow2_inputs' narrower variant for the long cut cases: q over the full range with -128 and 127 planted, x in {-1, 0, 1}, every scale 2^0 or 2^1 -- 4 * 128 k stays
+    below 2^24 up to k = 32767. The tests assert exactness_condition on what they draw."""
+    q, s, _, xs = pow2_inputs(c, (0, 1), (0, 1), salt)
+    x = _q8.rng_of(c["name"], salt + 150).integers(-1, 2, (c["k"], c["n"], c["Z"])).astype(np.int8)
+    return q, s, x, xs
+
+
 def exactness_condition(q, s, x, xs):
     """(largest / smallest product of two scales) * max over outputs of sum |q||x|: below 2^24 every partial sum, in any order, is an integer multiple of the
     smallest scale product below 2^24 of them -- exact in f32 (as long as that product is a multiple of 2^-149)."""
@@ -111,6 +155,15 @@ def lane_map_inputs(c, identity):
         x = (((r * 3 + col * 5 + (r * col) % 7) % 251) - 125).astype(np.int8)[:, :, None].repeat(Z, 2)
     s = np.ldexp(np.float32(1), (np.arange(outs) % 3))[None, :, None].repeat(n_groups(k, c["G"]), 0).repeat(Z, 2).astype(np.float32)
     xs = np.ldexp(np.float32(1), (np.arange(n) % 2))[None, :, None].repeat(n_groups(k, c["Gx"]), 0).repeat(Z, 2).astype(np.float32)
+    return q, s, x, xs
+
+
+def cut_lane_map_inputs(c):
+    """lane_map_inputs' asymmetric operands with x narrowed to [-4, 4] (tests/_gemm_q8.py's pattern): at k = 1088 the full-range x would pass the sum bound; with it
+    (largest / smallest scale product = 8) * 1088 * 127 * 4 stays below 2^24."""
+    q, s, _, xs = lane_map_inputs(c, False)
+    r, col = np.arange(c["k"])[:, None], np.arange(c["n"])[None, :]
+    x = (((r * 3 + col * 5 + (r * col) % 7) % 9) - 4).astype(np.int8)[:, :, None].repeat(c["Z"], 2)
     return q, s, x, xs
 
 
@@ -192,7 +245,7 @@ def model32(q, s, x, xs, G, Gx, k_per_split=None):
 def query_kw(c, cus=256):
     """The wg_gemm_q8a8_query a call on the case's views fills (buffers are 256-byte aligned: a view's address modulo 16 is its offset's)."""
     k, outs, n, Z, G, Gx = c["k"], c["outputs"], c["n"], c["Z"], c["G"], c["Gx"]
-    (moff, mpad, gap), (xoff, xpad), (ooff, opad) = c["m"], c["x"], c["o"]
+    (moff, mpad, gap), (xoff, xpad), (ooff, opad, ogap) = c["m"], c["x"], out_view(c)
     ldm, ldx, ldo, lds, ldxs = k + mpad, k + xpad, outs + opad, n_groups(k, G) + 1, n_groups(k, Gx) + 2
     return dict(k=k, outputs=outs, n=n, mats=Z, group_rows=G, x_group_rows=Gx, ldm=ldm, lds=lds, ldx=ldx, ldxs=ldxs, ldo=ldo, m_batch=ldm * outs + gap, s_batch=lds * outs + 2,
-                x_batch=ldx * n, xs_batch=ldxs * n + 3, o_batch=ldo * n, m_addr16=moff % 16, x_addr16=xoff % 16, o_addr16=4 * ooff % 16, cus=cus)
+                x_batch=ldx * n, xs_batch=ldxs * n + 3, o_batch=ldo * n + ogap, m_addr16=moff % 16, x_addr16=xoff % 16, o_addr16=4 * ooff % 16, cus=cus)

@@ -43,6 +43,12 @@ CASES = [
     ("t4_3rhs", CHUNK + LOAD, WIDE, 3, 1, 96, (0, 0, 0), 0, "gemv_q4/t,nr=4,u=1,c=4,ns=1"),
     ("t4_8rhs", 2 * CHUNK + LOAD, WIDE, 8, 1, 4001, (0, 0, 0), 0, "gemv_q4/t,nr=8,u=1,c=4,ns=1"),
     ("t4_split", 16384, 4096, 1, 1, 96, (0, 0, 0), 0, "gemv_q4/t,nr=1,u=2,c=4,ns=2"),                           # 128 workgroups: cut in two (the floor: 8192 rows per split)
+    # the cut with more than one right-hand side, and with two matrices on t_2mats' strided views: the smallest shapes either tile is cut at on 256 CUs (two splits of
+    # the floor's 8192 rows; 4 columns per half-wave need 128 workgroups of 32 columns for every CU to have one)
+    ("t_3rhs_split", 2 * TRIP8, T_COLS + 1, 3, 1, 128, (0, 0, 0), 0, "gemv_q4/t,nr=4,u=4,c=1,ns=2"),
+    ("t_2mats_split", 2 * TRIP8, T_COLS + 1, 2, 2, 96, (32, 16, 48), 4, "gemv_q4/t,nr=2,u=8,c=1,ns=2"),      # 8192 is no multiple of 96: a group straddles the cut
+    ("t4_3rhs_split", 2 * TRIP8, 4096, 3, 1, 96, (0, 0, 0), 0, "gemv_q4/t,nr=4,u=1,c=4,ns=2"),
+    ("t4_2mats_split", 2 * TRIP8, 2048, 2, 2, 128, (32, 16, 48), 4, "gemv_q4/t,nr=2,u=2,c=4,ns=2"),
     # the element-by-element kernel: byte offset 1 with leading dimension + 3, 37 rows of bytes, vectors at float offset 1; everything aligned but m.rows % 16;
     # everything aligned but the vectors' offset
     ("any_t", 74, 5, 2, 2, 32, (1, 3, 5), 1, "gemv_q4/any_t"),
@@ -50,6 +56,9 @@ CASES = [
     ("any_t_vector", 128, 6, 1, 1, 64, (0, 0, 0), 1, "gemv_q4/any_t"),
 ]
 CASE_IDS = [c[0] for c in CASES]
+# the call that fills the workspace with NaN partials (its scales are NaN) before a cut case runs: 4 splits of 8192 rows, 8 x 1024 outputs each -- more than any
+# cut case writes, and another outputs x right-hand sides than any of them has
+DIRTY = ("dirty", 4 * TRIP8, 1024, 8, 1, 128, (0, 0, 0), 0, "gemv_q4/t,nr=8,u=4,c=1,ns=4")
 EXACT_CASES = CASES  # every case, the two cut ones included: exact_scale_exp(k) keeps (max scale / min scale) * 32 k below 2^24
 
 

@@ -49,6 +49,14 @@ CASES = [
     ("n_11rhs", False, CHUNK, 20, 11, 1, 16, (0, 0, 0), 0, "gemv_q8/n,nr=8,u=8,ns=1"),
     ("n_2mats", False, N_ROWS + PIECE, 37, 2, 2, 128, (32, 16, 48), 4, "gemv_q8/n,nr=2,u=8,ns=1"),
     ("n_split", False, PIECE, 65536, 1, 1, 16, (0, 0, 0), 0, "gemv_q8/n,nr=1,u=8,ns=1024"),                   # one workgroup of rows: 1024 splits of 64 columns
+    # the cut with more than one right-hand side, and with two matrices on t_2mats' strided views: the smallest shapes each cut leaf is cut at on 256 CUs (T: two
+    # splits of the floor's 4096 rows; T with 4 columns per half-wave needs 128 workgroups of 32 columns for every CU to have one; N: splits of 64 columns)
+    ("t_3rhs_split", True, 2 * TRIP8, T_COLS + 1, 3, 1, 128, (0, 0, 0), 0, "gemv_q8/t,nr=4,u=4,c=1,ns=2"),
+    ("t_2mats_split", True, 2 * TRIP8, T_COLS + 1, 2, 2, 48, (32, 16, 48), 4, "gemv_q8/t,nr=2,u=8,c=1,ns=2"),      # 4096 is no multiple of 48: a group straddles the cut
+    ("t4_3rhs_split", True, 2 * TRIP8, 4096, 3, 1, 48, (0, 0, 0), 0, "gemv_q8/t,nr=4,u=1,c=4,ns=2"),
+    ("t4_2mats_split", True, 2 * TRIP8, 2048, 2, 2, 128, (32, 16, 48), 4, "gemv_q8/t,nr=2,u=2,c=4,ns=2"),
+    ("n_3rhs_split", False, 3 * PIECE, 320, 3, 1, 32, (0, 0, 0), 0, "gemv_q8/n,nr=4,u=8,ns=5"),                     # 5 splits of 64 columns; 48 rows in groups of 32
+    ("n_2mats_split", False, N_ROWS + PIECE, 192, 2, 2, 128, (32, 16, 48), 4, "gemv_q8/n,nr=2,u=8,ns=3"),           # a second workgroup of 16 rows
     # the element-by-element kernels: matrix offset 1, leading dimension rows + 3, rows 37, vectors at offset 1
     ("any_t", True, 37, 5, 2, 1, 16, (1, 3, 5), 1, "gemv_q8/any_t"),
     ("any_n", False, 37, 70, 3, 2, 16, (1, 3, 5), 1, "gemv_q8/any_n"),
@@ -56,6 +64,9 @@ CASES = [
     ("any_n_vector", False, 64, 48, 1, 1, 64, (0, 0, 0), 1, "gemv_q8/any_n"),                                # everything aligned but the vectors' offset
 ]
 CASE_IDS = [c[0] for c in CASES]
+# the call that fills the workspace with NaN partials (its scales are NaN) before a cut case runs: N, 16 splits of 64 columns, 3072 x 16 partials -- more than any
+# cut case writes, and another outputs x right-hand sides than any of them has
+DIRTY = ("dirty", False, 3 * N_ROWS, 1024, 1, 1, 128, (0, 0, 0), 0, "gemv_q8/n,nr=1,u=8,ns=16")
 EXACT_CASES = [c for c in CASES if (c[2] if c[1] else c[3]) <= 2048]  # the exact operands need k <= 2048
 
 

@@ -55,6 +55,56 @@ def test_lane_map_inputs_are_exact_and_asymmetric():
     U.assert_same_class_bits(GQ.model32(q, s, x, case["G"]), truth.astype(np.float32), "lane_map")
 
 
+@pytest.mark.parametrize("dt", GQ.DTYPES)
+@pytest.mark.parametrize("case", GQ.CUT_CASES, ids=GQ.CUT_IDS)
+def test_cut_model_inside_the_gate(case, dt):
+    """The cut cases under the SAME gate, f32_gate(2 k, sum |s q x|): the combine pass adds fewer than ns roundings to the 2 k the gate allows. "pairwise" adds the
+    groups' scaled sums over halves, as a cut's partial sums are."""
+    q, s, x = GQ.random_inputs(case, dt)
+    assert q.min() == -8 and q.max() == 7 and np.array_equal(_q4.unpack(_q4.pack(q)), q)
+    assert np.array_equal(GQ.round16(dt, x), x), "x is not representable in the 16-bit type"
+    truth, sabs = GQ.truth64(q, s, x, case["G"])
+    for order in ("sequential", "pairwise"):
+        r = _q4.assert_within_gate(GQ.model32(q, s, x, case["G"], order), truth, case["k"], sabs, f"{case['name']} {dt} {order}")
+        assert r < 1.0
+
+
+@pytest.mark.parametrize("dt", GQ.DTYPES)
+@pytest.mark.parametrize("case", GQ.CUT_CASES, ids=GQ.CUT_IDS)
+def test_cut_exact_inputs_are_exact(case, dt):
+    """What test_cut_exact_operands runs: exact_inputs, whose scales are 2^-2 .. 2^2 up to k = 16384 and 2^0 .. 2^1 beyond."""
+    q, s, x = GQ.exact_inputs(case, dt)
+    assert (q[0::2] == -8).any() and (q[1::2] == -8).any() and (q[0::2] == 7).any() and (q[1::2] == 7).any(), "both ends in even and in odd rows"
+    assert np.array_equal(GQ.round16(dt, x), x) and np.abs(x).max() <= 4
+    assert _q4.exactness_condition(q, s, x) < 2.0 ** 24
+    truth, _ = GQ.truth64(q, s, x, case["G"])
+    want = truth.astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), truth) and np.count_nonzero(want) > want.size // 2
+
+
+def test_cut_lane_map_inputs_are_exact_and_asymmetric():
+    """lane_map_inputs at k = 1088 (2 splits of 544 rows: the first ends on half a double step, the second starts on the other half) needs no narrower ranges:
+    4 * 1088 * 8 * 4 < 2^24. Permutations of the weights' rows in the SECOND split only, a step handed across the cut and the two splits exchanged change the
+    integers."""
+    case = GQ.CUT_LANE_MAP
+    k = case["k"]
+    q, s, x = GQ.lane_map_inputs(case)
+    assert 4 * k * 8 * 4 < 2 ** 24 and _q4.exactness_condition(q, s, x) < 2.0 ** 24 and np.abs(x).max() <= 4 and q.min() == -8 and q.max() == 7
+    truth, _ = GQ.truth64(q, s, x, case["G"])
+    t = truth[:, :, 0]
+    assert not np.array_equal(t, t.T), "the product is symmetric: a swapped row / column would pass"
+    second = lambda p: np.concatenate([np.arange(544), 544 + p])  # noqa: E731
+    perms = {"nibbles swapped": second(np.arange(544).reshape(-1, 2)[:, ::-1].ravel()),
+             "the dwords of a lane swapped": second(np.arange(544).reshape(-1, 2, 8)[:, ::-1, :].ravel()),
+             "the half-wave exchange crossed": second(np.arange(544).reshape(-1, 2, 16)[:, ::-1, :].ravel()),
+             "the second split begun on a whole double step": second((np.arange(544) + 32) % 544),
+             "the first split's last step read twice": np.concatenate([np.arange(544), np.arange(512, 544), np.arange(576, k)]),
+             "the splits exchanged": np.concatenate([np.arange(544, k), np.arange(544)])}
+    for what, perm in perms.items():  # a k permutation (or a repeated step) applied to the weights only changes the result
+        assert len(perm) == k and not np.array_equal(GQ.truth64(q[perm], s, x, case["G"])[0], truth), what
+    U.assert_same_class_bits(GQ.model32(q, s, x, case["G"], "pairwise"), truth.astype(np.float32), "cut_lane_map")
+
+
 def test_the_f16_unpack_identities_hold_for_all_16_nibbles():
     n = np.arange(16)
     lo = (np.uint16(0x6400) | n.astype(np.uint16)).view(np.float16)            # (b & 0x000f) | 0x6400

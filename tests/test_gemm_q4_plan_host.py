@@ -154,5 +154,81 @@ def test_the_plans_the_gpu_cases_pin():
     assert plan(**GQ.query_kw(cut, "bf16"))[2] == "gemm_q4/mfma,bf16,nt=2,ns=128 gemm_q4/combine,ns=128"
 
 
+# ---- the cut cases -------------------------------------------------------------------------------------------------------------------------------------
+# name: (nsplit, k_per_split, col_tiles, col_passes) on 256 CUs; k_per_split in logical rows
+CUT_PLANS = {
+    "cut_odd_steps": (2, 544, 2, 1), "cut_short_last": (3, 544, 2, 1), "cut_g96_partial": (2, 576, 2, 1), "cut_g64_views": (2, 576, 2, 1),
+    "cut_per_column": (2, 544, 2, 1), "cut_passes": (2, 544, 4, 2), "cut_passes_mats": (4, 512, 4, 3), "cut_ns5": (5, 512, 2, 1), "cut_ns29": (29, 512, 2, 1),
+    "cut_ns32": (32, 512, 2, 1), "cut_ns33": (33, 512, 2, 1), "cut_ns36": (36, 512, 2, 1), "cut_masked": (8, 512, 4, 3)}
+LAST_SPLIT = {"cut_short_last": 512, "cut_g96_partial": 544}  # rows of a last split shorter than the others
+GROUPS_PER_SPLIT = {"cut_odd_steps": 17, "cut_g96_partial": 6, "cut_g64_views": 9, "cut_per_column": 0, "cut_ns29": 0, "cut_ns32": 4}
+
+
+def check_cut_plan(c, q, p, tags, dt, want):
+    name = c["name"]
+    assert check(q, p, tags) == "mfma", name
+    assert (p.nsplit, p.k_per_split, p.col_tiles, p.col_passes) == want, (name, p.nsplit, p.k_per_split, p.col_tiles, p.col_passes)
+    assert p.workspace_bytes == c["Z"] * p.nsplit * c["n"] * c["outputs"] * 4, name
+    assert tags == f"gemm_q4/mfma,{dt},nt={want[2]},ns={want[0]} gemm_q4/combine,ns={want[0]}", (name, tags)
+    for b in range(0, c["k"], p.k_per_split):  # every split start: a whole step and, where the groups are shorter than k, a whole group
+        assert b % GQ.STEP == 0 and (c["G"] >= c["k"] or b % c["G"] == 0), (name, b)
+
+
+@pytest.mark.parametrize("dt", GQ.DTYPES)
+@pytest.mark.parametrize("case", GQ.CUT_CASES, ids=GQ.CUT_IDS)
+def test_the_cut_cases(case, dt):
+    """Every row of tests/_gemm_q4.py's CUT_CASES takes the MFMA leaf with the cut its comment names (and its tag carries), on the views the GPU test builds."""
+    q, p, tags = plan(**GQ.query_kw(case, dt, cus=256))
+    check_cut_plan(case, q, p, tags, dt, CUT_PLANS[case["name"]])
+    assert tags.split(" ")[0] == case["tag"].format(dt=dt)
+    if case["name"] in LAST_SPLIT:
+        assert case["k"] - (p.nsplit - 1) * p.k_per_split == LAST_SPLIT[case["name"]]
+    if case["name"] in GROUPS_PER_SPLIT:  # (the launcher's groups_per_split: k_per_split / G where G < k, else 0)
+        assert (p.k_per_split // case["G"] if case["G"] < case["k"] else 0) == GROUPS_PER_SPLIT[case["name"]]
+
+
+def odd_step_starts(c, dt="f16"):
+    """The split starts of a case that are an ODD multiple of 32 rows: such a split begins at byte offset 16 mod 32 of its column, in the middle of a double step, and the
+    split before it ends on half a double step."""
+    p = plan(**GQ.query_kw(c, dt))[1]
+    return [b for b in range(p.k_per_split, c["k"], p.k_per_split) if b // GQ.STEP % 2 == 1]
+
+
+def test_some_split_starts_on_an_odd_step():
+    """The kernel's guard `r + 32 h < r_end` and a split's first byte at 16 mod 32 are reached only by such a start: asserted, so that a change of the planner or of
+    the table cannot quietly take the cases off that line."""
+    assert odd_step_starts(GQ.by_name("cut_odd_steps")) == [544]
+    assert odd_step_starts(GQ.by_name("cut_short_last")) == [544]  # (1088 is even: the third split starts on a whole double step)
+    assert odd_step_starts(GQ.by_name("cut_per_column")) == [544] and odd_step_starts(GQ.by_name("cut_passes")) == [544] and odd_step_starts(GQ.CUT_LANE_MAP) == [544]
+    assert odd_step_starts(GQ.by_name("cut_g96_partial")) == []  # 576 = 18 steps
+    assert odd_step_starts(GQ.by_name("cut")) == []              # the older case: 512 rows per split never does
+
+
+def test_the_cut_tables_are_complete():
+    assert set(CUT_PLANS) == set(GQ.CUT_IDS) and len(set(GQ.CUT_IDS)) == len(GQ.CUT_IDS)
+    assert not set(GQ.CUT_IDS) & set(GQ.CASE_IDS)
+    # the combine's loops: every threshold at which waves 0 .. 3 take different loops, and the three ns the older cases have
+    assert {CUT_PLANS[n][0] for n in GQ.CUT_IDS} >= {2, 3, 4, 5, 29, 32, 33, 36}
+    for c, want in ((GQ.CUT_LANE_MAP, (2, 544, 2, 1)), (GQ.DIRTY, (8, 512, 4, 3))):
+        q, p, tags = plan(**GQ.query_kw(c, "f16"))
+        check_cut_plan(c, q, p, tags, "f16", want)
+
+
+def test_the_masked_cut_case_on_other_cu_counts():
+    """cut_masked: 12 workgroups (2 blocks of outputs x 3 passes x 2 matrices) against 4 x CUs -- three different cuts on 256, 16 and 8 CUs. The dirtying problem's
+    workspace covers the case's on each of them, and its outputs x n is another one."""
+    case = GQ.by_name("cut_masked")
+    for cus, want in ((256, (8, 512, 4, 3)), (16, (6, 704, 4, 3)), (8, (3, 1376, 4, 3))):
+        for dt in GQ.DTYPES:
+            q, p, tags = plan(**GQ.query_kw(case, dt, cus=cus))
+            check_cut_plan(case, q, p, tags, dt, want)
+    assert odd_step_starts(case) == []
+    for cus in (256, 16, 8):
+        dirty = plan(**GQ.query_kw(GQ.DIRTY, "f16", cus=cus))[1]
+        for c in GQ.CUT_CASES + [GQ.CUT_LANE_MAP]:
+            assert dirty.nsplit > 1 and dirty.workspace_bytes >= plan(**GQ.query_kw(c, "f16", cus=cus))[1].workspace_bytes, (cus, c["name"])
+            assert GQ.DIRTY["outputs"] * GQ.DIRTY["n"] != c["outputs"] * c["n"]
+
+
 def test_null_arguments():
     assert _lib.lib.wg_debug_gemm_q4_plan(None, None, None, 0) == _lib.WG_ERR_INVALID_ARG

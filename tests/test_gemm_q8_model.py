@@ -48,6 +48,52 @@ def test_lane_map_inputs_are_exact_and_asymmetric():
     U.assert_same_class_bits(GQ.model32(q, s, x, case["G"]), truth.astype(np.float32), "lane_map")
 
 
+@pytest.mark.parametrize("dt", GQ.DTYPES)
+@pytest.mark.parametrize("case", GQ.CUT_CASES, ids=GQ.CUT_IDS)
+def test_cut_model_inside_the_gate(case, dt):
+    """The cut cases under the SAME gate, f32_gate(2 k, sum |s q x|): the combine pass adds fewer than ns roundings to the 2 k the gate allows. "pairwise" adds the
+    groups' scaled sums over halves, as a cut's partial sums are."""
+    q, s, x = GQ.random_inputs(case, dt)
+    assert np.array_equal(GQ.round16(dt, x), x), "x is not representable in the 16-bit type"
+    truth, sabs = GQ.truth64(q, s, x, case["G"])
+    for order in ("sequential", "pairwise"):
+        r = _q8.assert_within_gate(GQ.model32(q, s, x, case["G"], order), truth, case["k"], sabs, f"{case['name']} {dt} {order}")
+        assert r < 1.0
+
+
+@pytest.mark.parametrize("dt", GQ.DTYPES)
+@pytest.mark.parametrize("case", GQ.CUT_CASES, ids=GQ.CUT_IDS)
+def test_cut_exact_inputs_are_exact(case, dt):
+    """What test_cut_exact_operands runs: exact_inputs up to k = 2048, the narrower variant (x in {-1, 0, 1}, scales 2^0 and 2^1) beyond."""
+    q, s, x = GQ.cut_exact_inputs(case, dt)
+    assert (q == -128).any() and (q == 127).any()
+    assert np.array_equal(GQ.round16(dt, x), x) and np.abs(x).max() == (4 if case["k"] <= 2048 else 1)
+    assert _q8.exactness_condition(q, s, x, True) < 2.0 ** 24
+    assert 2 * 128 * 18432 < 2 ** 24  # (the narrow variant's worst case at the longest k)
+    truth, _ = GQ.truth64(q, s, x, case["G"])
+    want = truth.astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), truth) and np.count_nonzero(want) > want.size // 2
+
+
+def test_cut_lane_map_inputs_are_exact_and_asymmetric():
+    """lane_map_inputs at k = 1088 (2 splits of 544 rows) needs no narrower ranges: 4 * 1088 * 127 * 4 < 2^24. A k permutation applied to one operand in the SECOND
+    split only, and the two splits' rows exchanged on one operand, change the integers."""
+    case = GQ.CUT_LANE_MAP
+    k = case["k"]
+    q, s, x = GQ.lane_map_inputs(case)
+    assert 4 * k * 127 * 4 < 2 ** 24 and _q8.exactness_condition(q, s, x, True) < 2.0 ** 24 and np.abs(x).max() <= 4 and q.min() >= -127
+    truth, _ = GQ.truth64(q, s, x, case["G"])
+    t = truth[:, :, 0]
+    assert not np.array_equal(t, t.T), "the product is symmetric: a swapped row / column would pass"
+    inside = np.arange(k)
+    inside[544:] = 544 + np.arange(544).reshape(-1, 2, 8)[:, ::-1, :].ravel()  # the halves of a lane's 16-byte piece swapped, in the second split
+    shifted = np.concatenate([np.arange(544), 544 + (np.arange(544) + 32) % 544])  # the second split's steps rotated by one
+    swapped = np.concatenate([np.arange(544, k), np.arange(544)])                  # the two splits' rows exchanged
+    for what, perm in (("inside a piece", inside), ("steps rotated", shifted), ("splits exchanged", swapped)):
+        assert not np.array_equal(GQ.truth64(q[perm], s, x, case["G"])[0], truth), what
+    U.assert_same_class_bits(GQ.model32(q, s, x, case["G"], "pairwise"), truth.astype(np.float32), "cut_lane_map")
+
+
 def test_int8_round_trips_through_both_16_bit_types():
     v = np.arange(-128, 128).astype(np.int8)
     assert np.array_equal(v.astype(np.float16).astype(np.int32), v.astype(np.int32))

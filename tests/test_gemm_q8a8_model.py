@@ -65,6 +65,70 @@ def test_power_of_two_operands_are_exact():
     U.assert_bits_equal(GA.model32(q, s, x, xs, c["G"], c["Gx"]), want, "2^-140")
 
 
+def cut_plan(case, cus=256):
+    """The planner's cut of a case (wg_debug_gemm_q8a8_plan on the query the GPU test's views fill)."""
+    import ctypes
+
+    from wgmath_amd import _lib
+    q, p = _lib.GemmQ8A8QueryC(), _lib.GemmQ8A8PlanC()
+    for key, v in GA.query_kw(case, cus=cus).items():
+        setattr(q, key, v)
+    tags = ctypes.create_string_buffer(128)
+    assert _lib.lib.wg_debug_gemm_q8a8_plan(ctypes.byref(q), ctypes.byref(p), tags, 128) == 0
+    return p
+
+
+@pytest.mark.parametrize("case", GA.CUT_CASES, ids=GA.CUT_IDS)
+def test_cut_model_within_the_gate(case):
+    """The cut cases under the planner's own cut: every cut boundary is a chain boundary (model32 asserts it), and the model -- the bits the GPU test asks for -- is
+    inside gate(nchains, sabs): the combine adds fewer than ns roundings, and an output of C chains is allowed 2 C."""
+    plan = cut_plan(case)
+    assert plan.nsplit > 1
+    q, s, x, xs = GA.random_inputs(case)
+    truth, sabs, nch = GA.truth64(q, s, x, xs, case["G"], case["Gx"])
+    assert plan.nsplit < nch + 1  # (no split without a chain of its own: the combine's roundings are fewer than the chains')
+    got = GA.model32(q, s, x, xs, case["G"], case["Gx"], plan.k_per_split)
+    err = np.abs(got.astype(np.float64) - truth)
+    tol = GA.gate(nch, sabs)
+    assert (err <= tol).all(), f"{case['name']}: worst err / gate = {(err / tol).max():.3g}"
+    if case["name"] == "cut_masked":  # the cuts of the 16- and 8-CU contexts
+        for cus in (16, 8):
+            got = GA.model32(q, s, x, xs, case["G"], case["Gx"], cut_plan(case, cus).k_per_split)
+            assert (np.abs(got.astype(np.float64) - truth) <= tol).all(), cus
+
+
+@pytest.mark.parametrize("case", GA.CUT_CASES, ids=GA.CUT_IDS)
+def test_cut_power_of_two_operands_are_exact(case):
+    """What test_cut_exact_operands runs (cut_pow2_inputs: x in {-1, 0, 1}, scales 2^0 and 2^1 on both sides): the condition holds and the model under the plan's cut
+    gives the float64 truth to the bit."""
+    q, s, x, xs = GA.cut_pow2_inputs(case)
+    assert (q == -128).any() and (q == 127).any() and np.abs(x).max() == 1
+    assert GA.exactness_condition(q, s, x, xs) < 2.0 ** 24 and 4 * 128 * 29696 < 2 ** 24
+    truth, _, _ = GA.truth64(q, s, x, xs, case["G"], case["Gx"])
+    want = truth.astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), truth) and np.count_nonzero(want) > want.size // 2
+    U.assert_same_class_bits(GA.model32(q, s, x, xs, case["G"], case["Gx"], cut_plan(case).k_per_split), want, case["name"])
+
+
+def test_cut_lane_map_inputs_are_exact_and_asymmetric():
+    """lane_map_inputs (an asymmetric x over the full int8 range) at k = 1088 is past the sum bound: x is narrowed to [-4, 4] -- 2 * 4 * 1088 * 127 * 4 < 2^24. A k
+    permutation applied to the weights in the SECOND split only, and the two splits exchanged, change the integers."""
+    case = GA.CUT_LANE_MAP
+    k = case["k"]
+    q, s, x, xs = GA.cut_lane_map_inputs(case)
+    assert 2 * 4 * k * 127 * 4 < 2 ** 24 and GA.exactness_condition(q, s, x, xs) < 2.0 ** 24 and np.abs(x).max() <= 4 and q.min() >= -127
+    truth, _, _ = GA.truth64(q, s, x, xs, case["G"], case["Gx"])
+    t = truth[:, :, 0]
+    assert not np.array_equal(t, t.T), "the product is symmetric: a swapped row / column would pass"
+    inside = np.arange(k)
+    inside[544:] = 544 + np.arange(544).reshape(-1, 2, 8)[:, ::-1, :].ravel()
+    shifted = np.concatenate([np.arange(544), 544 + (np.arange(544) + 32) % 544])
+    swapped = np.concatenate([np.arange(544, k), np.arange(544)])
+    for what, perm in (("inside a piece", inside), ("steps rotated", shifted), ("splits exchanged", swapped)):
+        assert not np.array_equal(GA.truth64(q[perm], s, x, xs, case["G"], case["Gx"])[0], truth), what
+    U.assert_same_class_bits(GA.model32(q, s, x, xs, case["G"], case["Gx"], 544), truth.astype(np.float32), "cut_lane_map")
+
+
 def test_combine_order():
     """The cut's partials are added as the combine pass adds them: wave w takes splits w, w + 4, ..., then ((w0 + w1) + w2) + w3 -- not ascending over all splits."""
     c = GA.by_name("cut")

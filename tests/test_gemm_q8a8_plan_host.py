@@ -171,5 +171,67 @@ def test_the_plans_the_gpu_cases_pin():
     assert plan(**GA.query_kw(GA.by_name("cut")))[2] == "gemm_q8a8/mfma,nt=2,ns=129 gemm_q8a8/combine,ns=129"
 
 
+# ---- the cut cases -------------------------------------------------------------------------------------------------------------------------------------
+# name: (nsplit, k_per_split, col_tiles, col_passes) on 256 CUs
+CUT_PLANS = {
+    "cut_odd_steps": (2, 544, 2, 1), "cut_short_last": (3, 544, 2, 1), "cut_g96_partial": (2, 576, 2, 1), "cut_g64_views": (2, 576, 2, 1),
+    "cut_per_column": (2, 1024, 2, 1), "cut_passes": (2, 544, 4, 2), "cut_passes_mats": (4, 512, 4, 3), "cut_ns5": (5, 512, 2, 1), "cut_ns29": (29, 1024, 2, 1),
+    "cut_ns32": (32, 512, 2, 1), "cut_ns33": (33, 512, 2, 1), "cut_ns36": (36, 512, 2, 1), "cut_masked": (8, 512, 4, 3),
+    "cut_w1536": (2, 1536, 2, 1), "cut_g64_128": (2, 640, 2, 1), "cut_x2048": (2, 2048, 4, 2), "cut_g32_whole": (2, 544, 2, 1)}
+LAST_SPLIT = {"cut_short_last": 512, "cut_g96_partial": 544, "cut_g64_128": 512}  # rows of a last split shorter than the others
+# the chains of each split where they are not simply the groups: (first row, rows) per chain
+SPLIT_CHAINS = {"cut_w1536": [(0, 1024), (1024, 512), (1536, 1024), (2560, 512)], "cut_x2048": [(0, 1024), (1024, 1024), (2048, 1024), (3072, 1024)],
+                "cut_per_column": [(0, 1024), (1024, 1024)]}
+
+
+def check_cut_plan(c, q, p, tags, want):
+    name = c["name"]
+    assert check(q, p, tags) == "mfma", name
+    assert (p.nsplit, p.k_per_split, p.col_tiles, p.col_passes) == want, (name, p.nsplit, p.k_per_split, p.col_tiles, p.col_passes)
+    assert p.workspace_bytes == c["Z"] * p.nsplit * c["n"] * c["outputs"] * 4, name
+    assert tags == f"gemm_q8a8/mfma,nt={want[2]},ns={want[0]} gemm_q8a8/combine,ns={want[0]}", (name, tags)
+    starts = list(range(0, c["k"], p.k_per_split))
+    for b in starts:  # every split start: a whole step and a whole group of each side that has groups
+        assert b % GA.STEP == 0 and all(G >= c["k"] or b % G == 0 for G in (c["G"], c["Gx"])), (name, b)
+    assert set(starts) <= GA.boundaries(c["k"], c["G"], c["Gx"]), name  # ... and a boundary of the model's own chains
+
+
+@pytest.mark.parametrize("case", GA.CUT_CASES, ids=GA.CUT_IDS)
+def test_the_cut_cases(case):
+    """Every row of tests/_gemm_q8a8.py's CUT_CASES takes the MFMA leaf with the cut its comment names (and its tag carries), on the views the GPU test builds."""
+    q, p, tags = plan(**GA.query_kw(case, cus=256))
+    check_cut_plan(case, q, p, tags, CUT_PLANS[case["name"]])
+    assert tags.split(" ")[0] == case["tag"]
+    if case["name"] in LAST_SPLIT:
+        assert case["k"] - (p.nsplit - 1) * p.k_per_split == LAST_SPLIT[case["name"]]
+    if case["name"] in SPLIT_CHAINS:
+        got = [ch for b in range(0, case["k"], p.k_per_split) for ch in GA.chains(case["k"], case["G"], case["Gx"], b, b + p.k_per_split)]
+        assert got == [(r0, r0 + rows) for r0, rows in SPLIT_CHAINS[case["name"]]], (case["name"], got)
+
+
+def test_the_cut_tables_are_complete():
+    assert set(CUT_PLANS) == set(GA.CUT_IDS) and len(set(GA.CUT_IDS)) == len(GA.CUT_IDS)
+    assert not set(GA.CUT_IDS) & set(GA.CASE_IDS)
+    # the combine's loops: every threshold at which waves 0 .. 3 take different loops, and the ns of the older kind
+    assert {CUT_PLANS[n][0] for n in GA.CUT_IDS} >= {2, 3, 4, 5, 29, 32, 33, 36}
+    for c, want in ((GA.CUT_LANE_MAP, (2, 544, 2, 1)), (GA.DIRTY, (8, 512, 4, 3))):
+        q, p, tags = plan(**GA.query_kw(c))
+        check_cut_plan(c, q, p, tags, want)
+
+
+def test_the_masked_cut_case_on_other_cu_counts():
+    """cut_masked: 12 workgroups (2 blocks of outputs x 3 passes x 2 matrices) against 4 x CUs -- three different cuts on 256, 16 and 8 CUs. The dirtying problem's
+    workspace covers the case's on each of them, and its outputs x n is another one."""
+    case = GA.by_name("cut_masked")
+    for cus, want in ((256, (8, 512, 4, 3)), (16, (6, 704, 4, 3)), (8, (3, 1376, 4, 3))):
+        q, p, tags = plan(**GA.query_kw(case, cus=cus))
+        check_cut_plan(case, q, p, tags, want)
+    for cus in (256, 16, 8):
+        dirty = plan(**GA.query_kw(GA.DIRTY, cus=cus))[1]
+        for c in GA.CUT_CASES + [GA.CUT_LANE_MAP]:
+            assert dirty.nsplit > 1 and dirty.workspace_bytes >= plan(**GA.query_kw(c, cus=cus))[1].workspace_bytes, (cus, c["name"])
+            assert GA.DIRTY["outputs"] * GA.DIRTY["n"] != c["outputs"] * c["n"]
+
+
 def test_null_arguments():
     assert _lib.lib.wg_debug_gemm_q8a8_plan(None, None, None, 0) == _lib.WG_ERR_INVALID_ARG

@@ -144,15 +144,47 @@ def test_grid_z_limit_is_the_q8_calls():
 def test_the_plans_the_gpu_cases_pin():
     """The tags tests/_q4.py expects on 256 CUs are the planner's (the GPU test reads them from the launch log)."""
     import _q4
-    for name, k, C, nrhs, Z, G, (moff, mpad, gap), voff, tag in _q4.CASES:
-        RB = k // 2
-        ldm, ldv = RB + mpad, k + (4 if voff else 0)
-        kw = dict(trans=1, rows=RB, cols=C, nrhs=nrhs, mats=Z, group_rows=G, cus=256, ldm=ldm, m_batch=ldm * C + gap, m_addr16=moff % 16, lds=-(-k // G),
-                  s_batch=-(-k // G) * C, ldv=ldv, v_batch=ldv * nrhs, v_addr16=4 * voff % 16, ldo=C + (4 if voff else 0), o_batch=(C + (4 if voff else 0)) * nrhs)
-        q, p, tags = plan(**kw)
+    for case in _q4.CASES:
+        name, tag = case[0], case[8]
+        q, p, tags = plan(**case_query(case))
         check(q, p, tags)
         assert tags.split(" ")[0] == tag, (name, tags)
         assert ("combine" in tags) == name.endswith("_split"), (name, tags)
+
+
+def case_query(case, cus=256):
+    """The query a call on the views tests/test_gpu_gemv_q4.py builds for a case fills."""
+    name, k, C, nrhs, Z, G, (moff, mpad, gap), voff, tag = case
+    RB = k // 2
+    ldm, ldv = RB + mpad, k + (4 if voff else 0)
+    return dict(trans=1, rows=RB, cols=C, nrhs=nrhs, mats=Z, group_rows=G, cus=cus, ldm=ldm, m_batch=ldm * C + gap, m_addr16=moff % 16, lds=-(-k // G),
+                s_batch=-(-k // G) * C, ldv=ldv, v_batch=ldv * nrhs, v_addr16=4 * voff % 16, ldo=C + (4 if voff else 0), o_batch=(C + (4 if voff else 0)) * nrhs)
+
+
+def test_the_cut_cases_with_more_right_hand_sides_and_matrices():
+    """The smallest shapes either tile is cut at on 256 CUs: name -> (columns per half-wave, nsplit, k_per_split, grid). One row of 8192 less, or (for the wide tile)
+    one workgroup of outputs less, and the planner does not cut / does not take that tile. The dirtying problem covers every cut case's workspace, on 256 and on the
+    248 CUs of the GPU test's masked context."""
+    import _q4
+    want = {"t_3rhs_split": (1, 2, 8192, (2, 2, 1)), "t_2mats_split": (1, 2, 8192, (2, 2, 2)), "t4_3rhs_split": (4, 2, 8192, (128, 2, 1)),
+            "t4_2mats_split": (4, 2, 8192, (64, 2, 2)), "t_split": (1, 8, 8192, (1, 8, 1)), "t4_split": (4, 2, 8192, (128, 2, 1))}
+    cut = {c[0]: c for c in _q4.CASES if c[0].endswith("_split")}
+    assert set(cut) == set(want)
+    for name, (cols, ns, per, grid) in want.items():
+        q, p, tags = plan(**case_query(cut[name]))
+        assert check(q, p, tags) == "t" and (p.cols, p.nsplit, p.k_per_split, tuple(p.grid)) == (cols, ns, per, grid), (name, p.cols, p.nsplit, p.k_per_split, tuple(p.grid))
+        assert p.workspace_bytes == 4 * q.mats * ns * q.nrhs * q.cols
+    for name in ("t_3rhs_split", "t_2mats_split", "t4_3rhs_split", "t4_2mats_split"):
+        c = cut[name]
+        assert plan(**case_query(c[:1] + (c[1] - 1024,) + c[2:]))[1].nsplit == 1, name  # one chunk of rows less: below two floors, not cut
+    for name in ("t4_3rhs_split", "t4_2mats_split"):
+        c = cut[name]
+        assert plan(**case_query(c[:2] + (c[2] - 32,) + c[3:]))[1].cols == 1, name  # one workgroup of outputs less: not every CU gets one, the narrow tile
+    for cus in (256, 248):
+        q, d, tags = plan(**case_query(_q4.DIRTY, cus))
+        assert check(q, d, tags) == "t" and d.nsplit > 1 and (cus != 256 or tags.split(" ")[0] == _q4.DIRTY[8])
+        for c in cut.values():
+            assert d.workspace_bytes >= plan(**case_query(c, cus))[1].workspace_bytes and _q4.DIRTY[2] * _q4.DIRTY[3] != c[2] * c[3], (cus, c[0])
 
 
 def test_null_arguments():

@@ -25,6 +25,8 @@ def test_models_stay_inside_the_gate_on_the_gpu_tests_inputs(case):
     if nrhs > 3:  # (the model is a Python loop per term: three right-hand sides of one matrix say what eleven would)
         v = v[:, :3]
     q, s, v = q[:, :, :1], s[:, :, :1], v[:, :, :1]
+    if name in ("t4_3rhs_split", "t4_2mats_split"):  # (t4_split's tile at the same size with more right-hand sides: 512 of the outputs -- they do not interact)
+        q, s = q[:, :512], s[:, :512]
     truth, sabs = _q8.truth64(q, s, v, G, tr)
     worst = {}
     for scale, order in _models_for(case):

@@ -123,15 +123,49 @@ def test_grid_z_limit_is_the_mixed_calls():
 def test_the_plans_the_gpu_cases_pin():
     """The tags tests/_q8.py expects on 256 CUs are the planner's (the GPU test reads them from the launch log)."""
     import _q8
-    for name, tr, R, C, nrhs, Z, G, (moff, mpad, gap), voff, tag in _q8.CASES:
-        k, outs = (R, C) if tr else (C, R)
-        ldm, ldv = R + mpad, k + (4 if voff else 0)
-        kw = dict(trans=int(tr), rows=R, cols=C, nrhs=nrhs, mats=Z, group_rows=G, cus=256, ldm=ldm, m_batch=ldm * C + gap, m_addr16=moff % 16, lds=-(-R // G),
-                  s_batch=-(-R // G) * C, ldv=ldv, v_batch=ldv * nrhs, v_addr16=4 * voff % 16, ldo=outs + (4 if voff else 0), o_batch=(outs + (4 if voff else 0)) * nrhs,
-                  o_addr16=4 * voff % 16)
-        q, p, tags = plan(**kw)
+    for case in _q8.CASES:
+        q, p, tags = plan(**case_query(case))
         check(q, p, tags)
-        assert tags.split(" ")[0] == tag, (name, tags)
+        assert tags.split(" ")[0] == case[9], (case[0], tags)
+        assert ("combine" in tags) == case[0].endswith("_split"), (case[0], tags)
+
+
+def case_query(case, cus=256):
+    """The query a call on the views tests/test_gpu_gemv_q8.py builds for a case fills."""
+    name, tr, R, C, nrhs, Z, G, (moff, mpad, gap), voff, tag = case
+    k, outs = (R, C) if tr else (C, R)
+    ldm, ldv = R + mpad, k + (4 if voff else 0)
+    return dict(trans=int(tr), rows=R, cols=C, nrhs=nrhs, mats=Z, group_rows=G, cus=cus, ldm=ldm, m_batch=ldm * C + gap, m_addr16=moff % 16, lds=-(-R // G),
+                s_batch=-(-R // G) * C, ldv=ldv, v_batch=ldv * nrhs, v_addr16=4 * voff % 16, ldo=outs + (4 if voff else 0), o_batch=(outs + (4 if voff else 0)) * nrhs,
+                o_addr16=4 * voff % 16)
+
+
+def test_the_cut_cases_with_more_right_hand_sides_and_matrices():
+    """The smallest shapes each cut leaf is cut at on 256 CUs: name -> (columns per half-wave, nsplit, k_per_split, grid). For T, one chunk of rows less, or (for
+    the wide tile) one workgroup of outputs less, and the planner does not cut / does not take that tile. The dirtying problem covers every cut case's workspace, on
+    256 and on the 248 CUs of the GPU test's masked context."""
+    import _q8
+    want = {"t_3rhs_split": (1, 2, 4096, (2, 2, 1)), "t_2mats_split": (1, 2, 4096, (2, 2, 2)), "t4_3rhs_split": (4, 2, 4096, (128, 2, 1)),
+            "t4_2mats_split": (4, 2, 4096, (64, 2, 2)), "n_3rhs_split": (1, 5, 64, (1, 5, 1)), "n_2mats_split": (1, 3, 64, (2, 3, 2)),
+            "t_split": (1, 16, 4096, (1, 16, 1)), "t4_split": (4, 2, 4096, (128, 2, 1)), "n_split": (1, 1024, 64, (1, 1024, 1))}
+    cut = {c[0]: c for c in _q8.CASES if c[0].endswith("_split")}
+    assert set(cut) == set(want)
+    for name, (cols, ns, per, grid) in want.items():
+        q, p, tags = plan(**case_query(cut[name]))
+        assert check(q, p, tags) == name[0] and (p.cols, p.nsplit, p.k_per_split, tuple(p.grid)) == (cols, ns, per, grid), (name, p.cols, p.nsplit, p.k_per_split, tuple(p.grid))
+        assert p.workspace_bytes == 4 * q.mats * ns * q.nrhs * (q.cols if q.trans else q.rows)
+    for name in ("t_3rhs_split", "t_2mats_split", "t4_3rhs_split", "t4_2mats_split"):
+        c = cut[name]
+        assert plan(**case_query(c[:2] + (c[2] - 512,) + c[3:]))[1].nsplit == 1, name  # one chunk of rows less: below two floors, not cut
+    for name in ("t4_3rhs_split", "t4_2mats_split"):
+        c = cut[name]
+        assert plan(**case_query(c[:3] + (c[3] - 32,) + c[4:]))[1].cols == 1, name  # one workgroup of outputs less: not every CU gets one, the narrow tile
+    for cus in (256, 248):
+        q, d, tags = plan(**case_query(_q8.DIRTY, cus))
+        assert check(q, d, tags) == "n" and d.nsplit > 1 and (cus != 256 or tags.split(" ")[0] == _q8.DIRTY[9])
+        for c in cut.values():
+            outs, douts = (c[3] if c[1] else c[2]), _q8.DIRTY[2]
+            assert d.workspace_bytes >= plan(**case_query(c, cus))[1].workspace_bytes and douts * _q8.DIRTY[4] != outs * c[4], (cus, c[0])
 
 
 def test_null_arguments():

@@ -13,6 +13,10 @@ tests/_q8.py's (tests/test_gemm_q8_model.py checks them on the CPU). The shapes 
   5  aliasing, on addresses                                                                                                test_aliasing
   6  WG_ERR_WORKSPACE inside a recording, success after wg_ctx_reserve_workspace; recorded + replayed = the eager bits     test_workspace_inside_a_recording
   7  the Python operators with quantize_q8                                                                                 test_python_operators
+  8  the cut contraction on GQ.CUT_CASES (more than one matrix and pass, T = 2, strided `out`, odd / short / group-straddling splits, every threshold of the combine's
+     two loops), each call on a workspace a NaN-scaled call of another shape has just filled: tags, truth, bits; exact operands; the lane map on 2 splits
+                                                                                                  test_cut_truth_on_a_dirty_workspace, test_cut_exact_operands, test_cut_lane_map
+  9  the cut recorded and replayed on dirtied workspaces, on the whole chip and on contexts of 16 and 8 CUs (three different ns)   test_cut_recorded_and_masked
 No test asserts a time.
 """
 import ctypes
@@ -109,27 +113,38 @@ def run(inst, G, dt, out, m, s, x):
 def build_case(gpu, c, dt, q, s, x):
     """The operands of a case on the device: the matrix at its byte offset / padding / gap, the scales in a view of their own that no kernel may assume dense (offset
     3, leading dimension + 1, gap 2), x and out at the case's offsets and paddings; `out` starts as NaN inside a NaN guard."""
-    (moff, mpad, gap), (xoff, xpad), (ooff, opad) = c["m"], c["x"], c["o"]
+    (moff, mpad, gap), (xoff, xpad), (ooff, opad, ogap) = c["m"], c["x"], GQ.out_view(c)
     m = Op(gpu, q, np.int8, off=moff, pad=mpad, gap=gap)
     sc = Op(gpu, s, off=3, pad=1, gap=2)
     xx = Op(gpu, GQ.bits16(dt, x), np.uint16, off=xoff, pad=xpad)
-    out = Op(gpu, np.full((c["outputs"], c["n"], c["Z"]), NAN32), off=ooff, pad=opad)
+    out = Op(gpu, np.full((c["outputs"], c["n"], c["Z"]), NAN32), off=ooff, pad=opad, gap=ogap)
     return m, sc, xx, out
 
 
 def planned_tags(gpu, c, dt, m, sc, xx, out):
     """wg_debug_gemm_q8_plan's tags for the query the call fills: the views' own strides and addresses, the context's CU count."""
+    return planned(gpu, c, dt, m, sc, xx, out)[1]
+
+
+def cus_of(inst):
+    """The CU count the launcher plans with: a CU-masked context's own."""
+    info = inst.adapter()
+    return info.get("stream_compute_units", info["compute_units"])
+
+
+def planned(gpu, c, dt, m, sc, xx, out, cus=None):
+    """(plan, tags) of wg_debug_gemm_q8_plan for the query the call fills; `cus`: another CU count than the context's."""
     L = _L()
     q, p = L.GemmQ8QueryC(), L.GemmQ8PlanC()
     kw = dict(k=c["k"], outputs=c["outputs"], n=c["n"], mats=c["Z"], group_rows=c["G"], x_bf16=int(dt == "bf16"), ldm=m.ld, lds=sc.ld, ldx=xx.ld, ldo=out.ld, m_batch=m.batch,
-              s_batch=sc.batch, x_batch=xx.batch, o_batch=out.batch, cus=gpu.adapter()["compute_units"])
+              s_batch=sc.batch, x_batch=xx.batch, o_batch=out.batch, cus=cus or cus_of(gpu))
     for name, op, es in (("m_addr16", m, 1), ("x_addr16", xx, 2), ("o_addr16", out, 4)):
         kw[name] = (L.lib.wg_buf_device_ptr(op.buf._h) + es * op.shape.offset) % 16
     for key, v in kw.items():
         setattr(q, key, v)
     tags = ctypes.create_string_buffer(128)
     assert L.lib.wg_debug_gemm_q8_plan(ctypes.byref(q), ctypes.byref(p), tags, 128) == 0
-    return tags.value.decode()
+    return p, tags.value.decode()
 
 
 # ---- 1 -------------------------------------------------------------------------------------------------------------------------------------------------
@@ -453,3 +468,177 @@ def test_python_operators(gpu, dt, G):
     gpu.queue().submit([enc.finish()])
     err = np.abs(tov.read(dev).astype(np.float64) - got[:, 0].astype(np.float64))
     assert (err <= 2 * _q8.gate(K, sabs[:, 0, 0])).all(), f"wg_gemv_q8 on the same weights: worst / (gate + gate) = {(err / (2 * _q8.gate(K, sabs[:, 0, 0]))).max():.3g}"
+
+
+# ---- 8 -------------------------------------------------------------------------------------------------------------------------------------------------
+_DIRTY, _SHARED = {}, {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _drop_shared():
+    yield
+    _DIRTY.clear()
+    _SHARED.clear()
+
+
+def shared(case, dt, kind):
+    """(q, s, x, truth, sabs) of a cut case, drawn and summed in float64 once for all the tests that use them (read-only)."""
+    key = (case["name"], dt, kind)
+    if key not in _SHARED:
+        q, s, x = GQ.random_inputs(case, dt) if kind == "random" else GQ.cut_exact_inputs(case, dt)
+        _SHARED[key] = (q, s, x) + tuple(GQ.truth64(q, s, x, case["G"]))
+        for a in _SHARED[key]:
+            a.setflags(write=False)
+    return _SHARED[key]
+
+
+def dirty_workspace(inst, dt, plan, case):
+    """One call on GQ.DIRTY (k 4096, 256 outputs, 192 columns) whose scales are all NaN: every f32 partial it writes into the context's workspace is NaN, so a partial
+    the next call fails to write shows in that call's result. Through the planner: the dirtying call is cut, and its workspace covers `plan`'s; its outputs x n is
+    another one than the case's, so stale values cannot line up."""
+    d = GQ.DIRTY
+    first = (id(inst), dt) not in _DIRTY
+    if first:
+        q, s, x = GQ.random_inputs(d, dt, salt=9)
+        _DIRTY[(id(inst), dt)] = (inst,) + build_case(inst, d, dt, q, np.full_like(s, NAN32), x)
+    m, sc, xx, out = _DIRTY[(id(inst), dt)][1:]
+    dplan, _ = planned(inst, d, dt, m, sc, xx, out)
+    assert dplan.nsplit > 1 and dplan.workspace_bytes >= plan.workspace_bytes > 0, (dplan.nsplit, dplan.workspace_bytes, plan.workspace_bytes)
+    assert d["outputs"] * d["n"] != case["outputs"] * case["n"]
+    run(inst, d["G"], dt, out, m, sc, xx)
+    if first:
+        assert np.isnan(out.read("dirty")).all(), "NaN scales did not reach every partial of the dirtying call"
+    inst.take_path()
+
+
+def assert_cut_tags(inst, case, dt, path, plan, tags):
+    """The logged tags are the planner's, the first is the case's (on 256 CUs; up to the cut elsewhere), the combine's tag follows; the ns logged."""
+    assert path == tags, f"{case['name']}: the call logged '{path}', the planner says '{tags}'"
+    first, want = path.split(" ")[0], case["tag"].format(dt=dt)
+    if cus_of(inst) == 256:
+        assert first == want, f"{case['name']}: expected {want}, the call took '{path}'"
+    else:
+        assert first.split(",ns=")[0] == want.split(",ns=")[0], f"{case['name']}: expected {want} up to the cut, the call took '{path}'"
+    ns = int(first.split("ns=")[1])
+    assert ns == plan.nsplit > 1 and path.split(" ")[1:] == [f"gemm_q8/combine,ns={ns}"], path
+    return ns
+
+
+@pytest.mark.parametrize("dt", GQ.DTYPES)
+@pytest.mark.parametrize("case", GQ.CUT_CASES, ids=GQ.CUT_IDS)
+def test_cut_truth_on_a_dirty_workspace(gpu, case, dt):
+    """A cut contraction whose workspace holds NaN in every partial the call should write: tags, every element written, nothing outside, the truth gate (the project's
+    f32_gate(2 k, sum |s q x|), not widened for the cut), and the same bits after dirtying again."""
+    name, k, G = case["name"], case["k"], case["G"]
+    q, s, x, truth, sabs = shared(case, dt, "random")
+    m, sc, xx, out = build_case(gpu, case, dt, q, s, x)
+    plan, tags = planned(gpu, case, dt, m, sc, xx, out)
+    dirty_workspace(gpu, dt, plan, case)
+    run(gpu, G, dt, out, m, sc, xx)
+    path = gpu.take_path()
+    got = out.read(name)  # (no byte outside the view changed)
+    ns = assert_cut_tags(gpu, case, dt, path, plan, tags)
+    print(f"{name} {dt} -> {path}: ns {ns} x {plan.k_per_split} rows")
+    assert not np.isnan(got).any(), f"{name}: {np.isnan(got).sum()} elements of the view are NaN: not written, or summed from a partial the call did not write"
+    r = _q8.assert_within_gate(got, truth, k, sabs, f"{name} {dt}")
+    print(f"  worst err / gate = {r:.3g}")
+    dirty_workspace(gpu, dt, plan, case)
+    out.poison()
+    run(gpu, G, dt, out, m, sc, xx)
+    U.assert_bits_equal(out.read(name), got, f"{name} {dt}: second call")
+
+
+@pytest.mark.parametrize("dt", GQ.DTYPES)
+@pytest.mark.parametrize("case", GQ.CUT_CASES, ids=GQ.CUT_IDS)
+def test_cut_exact_operands(gpu, case, dt):
+    """Exact operands under a cut (GQ.cut_exact_inputs: x in {-1, 0, 1} and scales 2^0, 2^1 past k = 2048; the condition is asserted): every partial sum in any order
+    is exact, so the result is fixed by construction -- a dropped, doubled or misplaced split gives other integers."""
+    name = case["name"]
+    q, s, x, truth, _ = shared(case, dt, "exact")
+    assert (q == -128).any() and (q == 127).any() and _q8.exactness_condition(q, s, x, True) < 2.0 ** 24
+    m, sc, xx, out = build_case(gpu, case, dt, q, s, x)
+    plan, tags = planned(gpu, case, dt, m, sc, xx, out)
+    dirty_workspace(gpu, dt, plan, case)
+    run(gpu, case["G"], dt, out, m, sc, xx)
+    assert_cut_tags(gpu, case, dt, gpu.take_path(), plan, tags)
+    want = truth.astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), truth)
+    U.assert_same_class_bits(out.read(name), want, f"{name} {dt}")
+
+
+@pytest.mark.parametrize("dt", GQ.DTYPES)
+def test_cut_lane_map(gpu, dt):
+    """test_lane_map's structured operands on 2 splits of 544 rows: a k permutation applied to one operand in the second split only, or a row / column slip in the
+    partials, gives other integers. The sum bound holds at this k without narrower ranges (asserted)."""
+    case = GQ.CUT_LANE_MAP
+    q, s, x = GQ.lane_map_inputs(case)
+    assert _q8.exactness_condition(q, s, x, True) < 2.0 ** 24
+    m, sc, xx, out = build_case(gpu, case, dt, q, s, x)
+    plan, tags = planned(gpu, case, dt, m, sc, xx, out)
+    dirty_workspace(gpu, dt, plan, case)
+    run(gpu, case["G"], dt, out, m, sc, xx)
+    assert_cut_tags(gpu, case, dt, gpu.take_path(), plan, tags)
+    truth, _ = GQ.truth64(q, s, x, case["G"])
+    U.assert_same_class_bits(out.read("cut_lane_map"), truth.astype(np.float32), f"cut_lane_map {dt}")
+
+
+# ---- 9 -------------------------------------------------------------------------------------------------------------------------------------------------
+SMALL = {"cus16": 16, "cus8": 8}
+
+
+@pytest.fixture(scope="module")
+def small():
+    wg = _wg()
+    made = {where: wg.GpuInstance.new(0, cu_count=n) for where, n in SMALL.items()}
+    yield made
+    for inst in made.values():
+        inst.sync()
+
+
+@pytest.mark.parametrize("where", ["whole", "cus16", "cus8"])
+def test_cut_recorded_and_masked(gpu, small, where):
+    """The cut on the whole chip and on contexts of 16 and 8 CUs (want_blocks = 4 x CUs decides ns): eagerly on a dirtied workspace -- the planner's tags for that CU
+    count, the truth gate -- then recorded once and replayed twice, the workspace dirtied and `out` poisoned before each replay: the eager bits. cut_masked is cut
+    differently on each of the three contexts, and on exact operands gives the same bits on all of them (the truth's)."""
+    inst = gpu if where == "whole" else small[where]
+    cus = dict(SMALL, whole=gpu.adapter()["compute_units"])
+    assert cus_of(inst) == cus[where]
+    for name, dt in (("cut_masked", "f16"), ("cut_masked", "bf16"), ("cut_g96_partial", "bf16"), ("cut_passes", "f16")):
+        case = GQ.by_name(name)
+        q, s, x, truth, sabs = shared(case, dt, "random")
+        m, sc, xx, out = build_case(inst, case, dt, q, s, x)
+        plan, tags = planned(inst, case, dt, m, sc, xx, out)
+        dirty_workspace(inst, dt, plan, case)
+        run(inst, case["G"], dt, out, m, sc, xx)
+        log = inst.take_path()
+        assert_cut_tags(inst, case, dt, log, plan, tags)
+        print(f"{name} {dt} {where} -> {log}: {plan.k_per_split} rows per split")
+        if name == "cut_masked":
+            ns = {w: planned(inst, case, dt, m, sc, xx, out, cus=n)[0].nsplit for w, n in cus.items()}
+            assert len(set(ns.values())) == 3 and plan.nsplit == ns[where], ns
+            assert cus["whole"] != 256 or ns == {"whole": 8, "cus16": 6, "cus8": 3}, ns
+        eager = out.read(name)
+        assert not np.isnan(eager).any()
+        _q8.assert_within_gate(eager, truth, case["k"], sabs, f"{name} {dt} {where}")
+        inst.device().reserve_workspace(plan.workspace_bytes)
+        out.poison()
+        enc = inst.device().create_command_encoder(record=True)
+        try:
+            run(inst, case["G"], dt, out, m, sc, xx)
+        finally:
+            cb = enc.finish()
+        assert inst.take_path() == log
+        for rep in range(2):
+            dirty_workspace(inst, dt, plan, case)
+            out.poison()
+            inst.queue().submit([cb])
+            U.assert_bits_equal(out.read(name), eager, f"{name} {dt} {where}: replay {rep}")
+        del cb
+        if name == "cut_masked":  # exact operands: the same bits whatever the cut
+            q, s, x, truth, _ = shared(case, dt, "exact")
+            assert _q8.exactness_condition(q, s, x, True) < 2.0 ** 24
+            m, sc, xx, out = build_case(inst, case, dt, q, s, x)
+            dirty_workspace(inst, dt, plan, case)
+            run(inst, case["G"], dt, out, m, sc, xx)
+            assert inst.take_path() == log
+            U.assert_same_class_bits(out.read(name), truth.astype(np.float32), f"{name} {dt} {where}: exact operands")

@@ -14,6 +14,10 @@ must EQUAL the float32 model to the bit: there is no tolerance. The shapes are t
   6  status codes and messages in the contract's order; aliasing on addresses                                           test_status_codes, test_aliasing
   7  WG_ERR_WORKSPACE inside a recording, success after wg_ctx_reserve_workspace; replayed = the eager bits             test_workspace_inside_a_recording
   8  the Python operators                                                                                               test_python_operators
+  9  the cut contraction on GA.CUT_CASES (more than one matrix and pass, T = 2, strided `out`, odd / short / group-straddling splits, every threshold of the
+     combine's two loops; chains of 1024 + 512 inside a split, G != Gx, one side grouped), each call on a workspace a NaN-scaled call of another shape has just
+     filled: tags, the model's bits, the gate; exact operands; the lane map on 2 splits   test_cut_truth_on_a_dirty_workspace, test_cut_exact_operands, test_cut_lane_map
+ 10  the cut recorded and replayed on dirtied workspaces, on the whole chip and on contexts of 16 and 8 CUs (three different ns)   test_cut_recorded_and_masked
 No test asserts a time.
 """
 import ctypes
@@ -105,21 +109,27 @@ def run(inst, G, Gx, out, m, s, x, xs):
 def build_case(gpu, c, q, s, x, xs):
     """The operands of a case on the device: the matrix and x at their byte offsets / paddings, both scales in views of their own that no kernel may assume dense,
     `out` at the case's offset and padding, NaN inside a NaN guard."""
-    (moff, mpad, gap), (xoff, xpad), (ooff, opad) = c["m"], c["x"], c["o"]
+    (moff, mpad, gap), (xoff, xpad), (ooff, opad, ogap) = c["m"], c["x"], GA.out_view(c)
     m = Op(gpu, q, np.int8, off=moff, pad=mpad, gap=gap)
     sc = Op(gpu, s, off=3, pad=1, gap=2)
     xx = Op(gpu, x, np.int8, off=xoff, pad=xpad)
     xsc = Op(gpu, xs, off=5, pad=2, gap=3)
-    out = Op(gpu, np.full((c["outputs"], c["n"], c["Z"]), NAN32), off=ooff, pad=opad)
+    out = Op(gpu, np.full((c["outputs"], c["n"], c["Z"]), NAN32), off=ooff, pad=opad, gap=ogap)
     return m, sc, xx, xsc, out
 
 
-def planned(gpu, c, m, sc, xx, xsc, out):
-    """wg_debug_gemm_q8a8_plan's (plan, tags) for the query the call fills: the views' own strides and addresses, the context's CU count."""
+def cus_of(inst):
+    """The CU count the launcher plans with: a CU-masked context's own."""
+    info = inst.adapter()
+    return info.get("stream_compute_units", info["compute_units"])
+
+
+def planned(gpu, c, m, sc, xx, xsc, out, cus=None):
+    """wg_debug_gemm_q8a8_plan's (plan, tags) for the query the call fills: the views' own strides and addresses, the context's CU count (or `cus`)."""
     L = _L()
     q, p = L.GemmQ8A8QueryC(), L.GemmQ8A8PlanC()
     kw = dict(k=c["k"], outputs=c["outputs"], n=c["n"], mats=c["Z"], group_rows=c["G"], x_group_rows=c["Gx"], ldm=m.ld, lds=sc.ld, ldx=xx.ld, ldxs=xsc.ld, ldo=out.ld,
-              m_batch=m.batch, s_batch=sc.batch, x_batch=xx.batch, xs_batch=xsc.batch, o_batch=out.batch, cus=gpu.adapter()["compute_units"])
+              m_batch=m.batch, s_batch=sc.batch, x_batch=xx.batch, xs_batch=xsc.batch, o_batch=out.batch, cus=cus or cus_of(gpu))
     for name, op, es in (("m_addr16", m, 1), ("x_addr16", xx, 1), ("o_addr16", out, 4)):
         kw[name] = (L.lib.wg_buf_device_ptr(op.buf._h) + es * op.shape.offset) % 16
     for key, v in kw.items():
@@ -471,3 +481,192 @@ def test_python_operators(gpu, G, Gx):
         finally:
             p.end()
             gpu.queue().submit([enc.finish()])
+
+
+# ---- 9 -------------------------------------------------------------------------------------------------------------------------------------------------
+_DIRTY, _SHARED = {}, {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _drop_shared():
+    yield
+    _DIRTY.clear()
+    _SHARED.clear()
+
+
+def shared(case, kind):
+    """(q, s, x, xs, truth, sabs, chains) of a cut case, drawn and summed in float64 once for all the tests that use them (read-only)."""
+    key = (case["name"], kind)
+    if key not in _SHARED:
+        ins = GA.random_inputs(case) if kind == "random" else GA.cut_pow2_inputs(case)
+        truth, sabs, nch = GA.truth64(*ins, case["G"], case["Gx"])
+        for a in ins + (truth, sabs):
+            a.setflags(write=False)
+        _SHARED[key] = ins + (truth, sabs, nch)
+    return _SHARED[key]
+
+
+def model_of(case, kps, kind="random"):
+    """GA.model32 of the shared inputs under a cut of `kps` rows per split, once per cut."""
+    key = (case["name"], kind, "model", kps)
+    if key not in _SHARED:
+        _SHARED[key] = GA.model32(*shared(case, kind)[:4], case["G"], case["Gx"], kps)
+        _SHARED[key].setflags(write=False)
+    return _SHARED[key]
+
+
+def dirty_workspace(inst, plan, case):
+    """One call on GA.DIRTY (k 4096, 256 outputs, 192 columns) whose weight scales are all NaN: every f32 partial it writes into the context's workspace is NaN, so a
+    partial the next call fails to write shows in that call's result. Through the planner: the dirtying call is cut, and its workspace covers `plan`'s; its
+    outputs x n is another one than the case's, so stale values cannot line up."""
+    d = GA.DIRTY
+    first = id(inst) not in _DIRTY
+    if first:
+        q, s, x, xs = GA.random_inputs(d, salt=9)
+        _DIRTY[id(inst)] = (inst,) + build_case(inst, d, q, np.full_like(s, NAN32), x, xs)
+    m, sc, xx, xsc, out = _DIRTY[id(inst)][1:]
+    dplan, _ = planned(inst, d, m, sc, xx, xsc, out)
+    assert dplan.nsplit > 1 and dplan.workspace_bytes >= plan.workspace_bytes > 0, (dplan.nsplit, dplan.workspace_bytes, plan.workspace_bytes)
+    assert d["outputs"] * d["n"] != case["outputs"] * case["n"]
+    run(inst, d["G"], d["Gx"], out, m, sc, xx, xsc)
+    if first:
+        assert np.isnan(out.read("dirty")).all(), "NaN scales did not reach every partial of the dirtying call"
+    inst.take_path()
+
+
+def assert_cut_tags(inst, case, path, plan, tags):
+    """The logged tags are the planner's, the first is the case's (on 256 CUs; up to the cut elsewhere), the combine's tag follows; the ns logged."""
+    assert path == tags, f"{case['name']}: the call logged '{path}', the planner says '{tags}'"
+    first, want = path.split(" ")[0], case["tag"]
+    if cus_of(inst) == 256:
+        assert first == want, f"{case['name']}: expected {want}, the call took '{path}'"
+    else:
+        assert first.split(",ns=")[0] == want.split(",ns=")[0], f"{case['name']}: expected {want} up to the cut, the call took '{path}'"
+    ns = int(first.split("ns=")[1])
+    assert ns == plan.nsplit > 1 and path.split(" ")[1:] == [f"gemm_q8a8/combine,ns={ns}"], path
+    return ns
+
+
+@pytest.mark.parametrize("case", GA.CUT_CASES, ids=GA.CUT_IDS)
+def test_cut_truth_on_a_dirty_workspace(gpu, case):
+    """A cut contraction whose workspace holds NaN in every partial the call should write: tags, every element written, nothing outside, the gate (2 rounded terms per
+    chain, not widened for the cut), the bits of the model under the plan's cut, and the same bits after dirtying again."""
+    name, G, Gx = case["name"], case["G"], case["Gx"]
+    q, s, x, xs, truth, sabs, nch = shared(case, "random")
+    m, sc, xx, xsc, out = build_case(gpu, case, q, s, x, xs)
+    plan, tags = planned(gpu, case, m, sc, xx, xsc, out)
+    dirty_workspace(gpu, plan, case)
+    run(gpu, G, Gx, out, m, sc, xx, xsc)
+    path = gpu.take_path()
+    got = out.read(name)  # (no byte outside the view changed)
+    ns = assert_cut_tags(gpu, case, path, plan, tags)
+    print(f"{name} -> {path}: ns {ns} x {plan.k_per_split} rows")
+    assert not np.isnan(got).any(), f"{name}: {np.isnan(got).sum()} elements of the view are NaN: not written, or summed from a partial the call did not write"
+    err, tol = np.abs(got.astype(np.float64) - truth), GA.gate(nch, sabs)
+    print(f"  worst |got - truth| / gate = {(err / tol).max():.3g}")
+    assert (err <= tol).all(), f"{name}: {(err > tol).sum()} elements outside gate({nch} chains); worst err / gate = {(err / tol).max():.3g}"
+    U.assert_bits_equal(got, model_of(case, plan.k_per_split), f"{name}: against the float32 model")
+    dirty_workspace(gpu, plan, case)
+    out.poison()
+    run(gpu, G, Gx, out, m, sc, xx, xsc)
+    U.assert_bits_equal(out.read(name), got, f"{name}: second call")
+
+
+@pytest.mark.parametrize("case", GA.CUT_CASES, ids=GA.CUT_IDS)
+def test_cut_exact_operands(gpu, case):
+    """Exact operands under a cut (GA.cut_pow2_inputs: x in {-1, 0, 1}, scales 2^0 and 2^1 on both sides; the condition is asserted): every partial sum in any order is
+    exact, so the result is fixed by construction -- the float64 truth, which is also the model's bits. A dropped, doubled or misplaced split gives other integers."""
+    name = case["name"]
+    q, s, x, xs, truth, _, _ = shared(case, "exact")
+    assert (q == -128).any() and (q == 127).any() and GA.exactness_condition(q, s, x, xs) < 2.0 ** 24
+    m, sc, xx, xsc, out = build_case(gpu, case, q, s, x, xs)
+    plan, tags = planned(gpu, case, m, sc, xx, xsc, out)
+    dirty_workspace(gpu, plan, case)
+    run(gpu, case["G"], case["Gx"], out, m, sc, xx, xsc)
+    assert_cut_tags(gpu, case, gpu.take_path(), plan, tags)
+    want = truth.astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), truth)
+    got = out.read(name)
+    U.assert_same_class_bits(got, want, name)
+    U.assert_same_class_bits(got, model_of(case, plan.k_per_split, "exact"), f"{name}: against the float32 model")
+
+
+def test_cut_lane_map(gpu):
+    """test_lane_map's asymmetric operands, x narrowed to [-4, 4] for the sum bound at this k (asserted), on 2 splits of 544 rows: a k permutation applied to one
+    operand in the second split only, or a row / column slip in the partials, gives other integers."""
+    case = GA.CUT_LANE_MAP
+    q, s, x, xs = GA.cut_lane_map_inputs(case)
+    assert GA.exactness_condition(q, s, x, xs) < 2.0 ** 24
+    m, sc, xx, xsc, out = build_case(gpu, case, q, s, x, xs)
+    plan, tags = planned(gpu, case, m, sc, xx, xsc, out)
+    dirty_workspace(gpu, plan, case)
+    run(gpu, case["G"], case["Gx"], out, m, sc, xx, xsc)
+    assert_cut_tags(gpu, case, gpu.take_path(), plan, tags)
+    truth, _, _ = GA.truth64(q, s, x, xs, case["G"], case["Gx"])
+    want = truth.astype(np.float32)
+    assert np.array_equal(want.astype(np.float64), truth)
+    U.assert_same_class_bits(out.read("cut_lane_map"), want, "cut_lane_map")
+
+
+# ---- 10 ------------------------------------------------------------------------------------------------------------------------------------------------
+SMALL = {"cus16": 16, "cus8": 8}
+
+
+@pytest.fixture(scope="module")
+def small():
+    wg = _wg()
+    made = {where: wg.GpuInstance.new(0, cu_count=n) for where, n in SMALL.items()}
+    yield made
+    for inst in made.values():
+        inst.sync()
+
+
+@pytest.mark.parametrize("where", ["whole", "cus16", "cus8"])
+def test_cut_recorded_and_masked(gpu, small, where):
+    """The cut on the whole chip and on contexts of 16 and 8 CUs (want_blocks = 4 x CUs decides ns): eagerly on a dirtied workspace -- the planner's tags for that CU
+    count, the gate, the model's bits under that context's cut -- then recorded once and replayed twice, the workspace dirtied and `out` poisoned before each replay:
+    the eager bits. cut_masked is cut differently on each of the three contexts, and on exact operands gives the same bits on all of them (the truth's)."""
+    inst = gpu if where == "whole" else small[where]
+    cus = dict(SMALL, whole=cus_of(gpu))
+    assert cus_of(inst) == cus[where]
+    for name in ("cut_masked", "cut_g96_partial", "cut_passes"):
+        case = GA.by_name(name)
+        G, Gx = case["G"], case["Gx"]
+        q, s, x, xs, truth, sabs, nch = shared(case, "random")
+        m, sc, xx, xsc, out = build_case(inst, case, q, s, x, xs)
+        plan, tags = planned(inst, case, m, sc, xx, xsc, out)
+        dirty_workspace(inst, plan, case)
+        run(inst, G, Gx, out, m, sc, xx, xsc)
+        log = inst.take_path()
+        assert_cut_tags(inst, case, log, plan, tags)
+        print(f"{name} {where} -> {log}: {plan.k_per_split} rows per split")
+        if name == "cut_masked":
+            ns = {w: planned(inst, case, m, sc, xx, xsc, out, cus=n)[0].nsplit for w, n in cus.items()}
+            assert len(set(ns.values())) == 3 and plan.nsplit == ns[where], ns
+            assert cus["whole"] != 256 or ns == {"whole": 8, "cus16": 6, "cus8": 3}, ns
+        eager = out.read(name)
+        assert not np.isnan(eager).any()
+        assert (np.abs(eager.astype(np.float64) - truth) <= GA.gate(nch, sabs)).all(), f"{name} {where}: outside the gate"
+        U.assert_bits_equal(eager, model_of(case, plan.k_per_split), f"{name} {where}: against the float32 model")
+        inst.device().reserve_workspace(plan.workspace_bytes)
+        out.poison()
+        enc = inst.device().create_command_encoder(record=True)
+        try:
+            run(inst, G, Gx, out, m, sc, xx, xsc)
+        finally:
+            cb = enc.finish()
+        assert inst.take_path() == log
+        for rep in range(2):
+            dirty_workspace(inst, plan, case)
+            out.poison()
+            inst.queue().submit([cb])
+            U.assert_bits_equal(out.read(name), eager, f"{name} {where}: replay {rep}")
+        del cb
+        if name == "cut_masked":  # exact operands: the same bits whatever the cut
+            q, s, x, xs, truth, _, _ = shared(case, "exact")
+            assert GA.exactness_condition(q, s, x, xs) < 2.0 ** 24
+            m, sc, xx, xsc, out = build_case(inst, case, q, s, x, xs)
+            dirty_workspace(inst, plan, case)
+            run(inst, G, Gx, out, m, sc, xx, xsc)
+            assert inst.take_path() == log
+            U.assert_same_class_bits(out.read(name), truth.astype(np.float32), f"{name} {where}: exact operands")

@@ -12,6 +12,8 @@ tests/_q4.py's (tests/test_gemv_q4_model.py checks them on the CPU).
   5  against wg_gemv_q8 on the unpacked int8: to the bit on exact operands, within twice the gate    test_against_wg_gemv_q8
   6  NaN in out overwritten; NaN / Inf in v or in a scale reach exactly their outputs; 0 * Inf = NaN  test_special_values
   7  the same call twice is bit-identical, the cut contraction included                               (in 1)
+     every cut case (1 and 3 right-hand sides, 1 and 2 matrices, either tile) runs on a workspace that a NaN-scaled call of another shape has just filled, in 1, 3
+     and 10: an unwritten partial is a NaN in the result                                              dirty_workspace
   8  status codes and messages, out = W v among them                                                  test_status_codes, test_workspace_inside_a_recording
   9  aliasing, on addresses                                                                          test_aliasing
  10  recorded and replayed; a CU-masked context                                                      test_recorded_and_masked
@@ -116,6 +118,55 @@ def build_case(gpu, case, q, s, v):
     return m, sc, vv, out
 
 
+_DIRTY = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _drop_dirty():
+    yield
+    _DIRTY.clear()
+
+
+def planned(inst, case, m, sc, vv, out):
+    """wg_debug_gemv_q4_plan's plan for the query a call on these views fills, on the context's CU count (a CU-masked context's own)."""
+    L = _L()
+    name, k, C, nrhs, Z, G = case[:6]
+    info = inst.adapter()
+    q, p = L.GemvQ4QueryC(), L.GemvQ4PlanC()
+    kw = dict(trans=1, rows=k // 2, cols=C, nrhs=nrhs, mats=Z, group_rows=G, ldm=m.ld, lds=sc.ld, ldv=vv.ld, ldo=out.ld, m_batch=m.batch, s_batch=sc.batch, v_batch=vv.batch,
+              o_batch=out.batch, cus=info.get("stream_compute_units", info["compute_units"]))
+    for key, op, es in (("m_addr16", m, 1), ("v_addr16", vv, 4)):
+        kw[key] = (L.lib.wg_buf_device_ptr(op.buf._h) + es * op.shape.offset) % 16
+    for key, v in kw.items():
+        setattr(q, key, v)
+    tags = ctypes.create_string_buffer(128)
+    assert L.lib.wg_debug_gemv_q4_plan(ctypes.byref(q), ctypes.byref(p), tags, 128) == 0
+    return p
+
+
+def dirty_workspace(inst, case, ops):
+    """Before a cut case (`ops`: its operands) runs: one call on _q4.DIRTY, a larger cut problem of another shape whose scales are all NaN, so that every f32 partial
+    in the context's workspace the case should write holds NaN -- a partial it fails to write shows in its result. Through the planner: the dirtying call is cut and
+    its workspace covers the case's; its outputs x right-hand sides is another one, so stale values cannot line up. Nothing happens for a case that is not cut."""
+    plan = planned(inst, case, *ops)
+    if plan.nsplit == 1:
+        return
+    d = _q4.DIRTY
+    first = id(inst) not in _DIRTY
+    if first:
+        q, s, v = _q4.random_inputs(d, salt=9)
+        _DIRTY[id(inst)] = (inst,) + build_case(inst, d, q, np.full_like(s, NAN32), v)
+    dops = _DIRTY[id(inst)][1:]
+    dplan = planned(inst, d, *dops)
+    assert dplan.nsplit > 1 and dplan.workspace_bytes >= plan.workspace_bytes > 0, (dplan.nsplit, dplan.workspace_bytes, plan.workspace_bytes)
+    assert d[2] * d[3] != case[2] * case[3]
+    m, sc, vv, out = dops
+    run(inst, d[5], out, m, sc, vv)
+    if first:
+        assert np.isnan(out.read("dirty")).all(), "NaN scales did not reach every partial of the dirtying call"
+    inst.take_path()
+
+
 def _raw(gpu, arr):
     """A buffer of exactly arr.nbytes bytes."""
     wg = _wg()
@@ -130,6 +181,7 @@ def test_leaves_truth_and_determinism(gpu, case):
     q, s, v = _q4.random_inputs(case)
     assert q.min() == -8 and q.max() == 7
     m, sc, vv, out = build_case(gpu, case, q, s, v)
+    dirty_workspace(gpu, case, (m, sc, vv, out))  # (a cut case: NaN in every partial it should write)
     gpu.take_path()
     run(gpu, G, out, m, sc, vv)
     path = gpu.take_path()
@@ -150,6 +202,7 @@ def test_leaves_truth_and_determinism(gpu, case):
     truth, sabs = _q4.truth64(q, s, v, G)
     _q4.assert_within_gate(got, truth, k, sabs, name)
     # 7: the same bits again
+    dirty_workspace(gpu, case, (m, sc, vv, out))
     out.poison()
     run(gpu, G, out, m, sc, vv)
     U.assert_bits_equal(out.read(name), got, f"{name}: second call")
@@ -164,6 +217,7 @@ def test_exact_operands(gpu, case):
     q, s, v = _q4.exact_inputs(case)
     assert (q == -8).any() and (q == 7).any() and _q4.exactness_condition(q, s, v) < 2.0 ** 24
     m, sc, vv, out = build_case(gpu, case, q, s, v)
+    dirty_workspace(gpu, case, (m, sc, vv, out))
     gpu.take_path()
     run(gpu, G, out, m, sc, vv)
     assert (" gemv_q4/combine,ns=" in gpu.take_path()) == name.endswith("_split"), name
@@ -515,22 +569,24 @@ def masked():
     inst.sync()
 
 
-REPLAY = [c for c in _q4.CASES if c[0] in ("t_trips", "t_8rhs", "t_split", "t4_8rhs", "t4_trips", "any_t")]
+REPLAY = [c for c in _q4.CASES if c[0] in ("t_trips", "t_8rhs", "t_split", "t4_8rhs", "t4_trips", "any_t", "t_3rhs_split", "t_2mats_split", "t4_3rhs_split", "t4_2mats_split")]
 
 
 @pytest.mark.parametrize("where", ["whole", "masked"])
 def test_recorded_and_masked(gpu, masked, where):
-    """Eager, then recorded once and replayed twice into a re-poisoned output: the eager bits each time. On the whole chip and on a CU-masked context (248 CUs: the
+    """Eager, then recorded once and replayed twice into a re-poisoned output (a cut case: on a workspace dirtied before the eager call and before each replay): the
+    eager bits each time. On the whole chip and on a CU-masked context (248 CUs: the
     plan reads the context's CU count), where the truth gate and determinism hold."""
     inst = gpu if where == "whole" else masked
     for case in REPLAY:
         name, k, C, nrhs, Z, G = case[:6]
         q, s, v = _q4.random_inputs(case, salt=3)
         m, sc, vv, out = build_case(inst, case, q, s, v)
+        dirty_workspace(inst, case, (m, sc, vv, out))
         inst.take_path()
         run(inst, G, out, m, sc, vv)
         log = inst.take_path()
-        assert log.startswith("gemv_q4/"), log
+        assert log.startswith("gemv_q4/") and (" gemv_q4/combine,ns=" in log) == name.endswith("_split"), (name, log)
         eager = out.read(name)
         truth, sabs = _q4.truth64(q, s, v, G)
         _q4.assert_within_gate(eager, truth, k, sabs, f"{name} {where}")
@@ -542,6 +598,7 @@ def test_recorded_and_masked(gpu, masked, where):
             cb = enc.finish()
         assert inst.take_path() == log
         for rep in range(2):
+            dirty_workspace(inst, case, (m, sc, vv, out))
             out.poison()
             inst.queue().submit([cb])
             U.assert_bits_equal(out.read(name), eager, f"{name} {where}: replay {rep}")

@@ -9,6 +9,8 @@ accumulator stored as it is; deterministic. Cases, inputs, truth and gate are te
   4  against wg_gemv_mixed on the dequantised f16 matrix and wg_gemv on the dequantised f32 one       test_against_the_projects_own_kernels
   5  NaN in out overwritten; NaN / Inf in v or in a scale reach exactly their outputs; 0 * Inf = NaN  test_special_values
   6  the same call twice is bit-identical, the cut contraction included                               (in 1)
+     every cut case (1 and 3 right-hand sides, 1 and 2 matrices, per cut leaf) runs on a workspace that a NaN-scaled call of another shape has just filled, in 1,
+     3 and 9: an unwritten partial is a NaN in the result                                             dirty_workspace
   7  status codes and messages                                                                       test_status_codes, test_workspace_inside_a_recording
   8  aliasing, on addresses                                                                          test_aliasing
   9  recorded and replayed; a CU-masked context                                                      test_recorded_and_masked
@@ -114,6 +116,55 @@ def build_case(gpu, case, q, s, v):
     return m, sc, vv, out
 
 
+_DIRTY = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _drop_dirty():
+    yield
+    _DIRTY.clear()
+
+
+def planned(inst, case, m, sc, vv, out):
+    """wg_debug_gemv_q8_plan's plan for the query a call on these views fills, on the context's CU count (a CU-masked context's own)."""
+    L = _L()
+    name, tr, R, C, nrhs, Z, G = case[:7]
+    info = inst.adapter()
+    q, p = L.GemvQ8QueryC(), L.GemvQ8PlanC()
+    kw = dict(trans=int(tr), rows=R, cols=C, nrhs=nrhs, mats=Z, group_rows=G, ldm=m.ld, lds=sc.ld, ldv=vv.ld, ldo=out.ld, m_batch=m.batch, s_batch=sc.batch, v_batch=vv.batch,
+              o_batch=out.batch, cus=info.get("stream_compute_units", info["compute_units"]))
+    for key, op, es in (("m_addr16", m, 1), ("v_addr16", vv, 4), ("o_addr16", out, 4)):
+        kw[key] = (L.lib.wg_buf_device_ptr(op.buf._h) + es * op.shape.offset) % 16
+    for key, v in kw.items():
+        setattr(q, key, v)
+    tags = ctypes.create_string_buffer(128)
+    assert L.lib.wg_debug_gemv_q8_plan(ctypes.byref(q), ctypes.byref(p), tags, 128) == 0
+    return p
+
+
+def dirty_workspace(inst, case, ops):
+    """Before a cut case (`ops`: its operands) runs: one call on _q8.DIRTY, a larger cut problem of another shape whose scales are all NaN, so that every f32 partial
+    in the context's workspace the case should write holds NaN -- a partial it fails to write shows in its result. Through the planner: the dirtying call is cut and
+    its workspace covers the case's; its outputs x right-hand sides is another one, so stale values cannot line up. Nothing happens for a case that is not cut."""
+    plan = planned(inst, case, *ops)
+    if plan.nsplit == 1:
+        return
+    d = _q8.DIRTY
+    first = id(inst) not in _DIRTY
+    if first:
+        q, s, v = _q8.random_inputs(d, salt=9)
+        _DIRTY[id(inst)] = (inst,) + build_case(inst, d, q, np.full_like(s, NAN32), v)
+    dops = _DIRTY[id(inst)][1:]
+    dplan = planned(inst, d, *dops)
+    assert dplan.nsplit > 1 and dplan.workspace_bytes >= plan.workspace_bytes > 0, (dplan.nsplit, dplan.workspace_bytes, plan.workspace_bytes)
+    assert d[2] * d[4] != (case[3] if case[1] else case[2]) * case[4]
+    m, sc, vv, out = dops
+    run(inst, d[1], d[6], out, m, sc, vv)
+    if first:
+        assert np.isnan(out.read("dirty")).all(), "NaN scales did not reach every partial of the dirtying call"
+    inst.take_path()
+
+
 # ---- 1, 2, 6 -------------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("case", _q8.CASES, ids=_q8.CASE_IDS)
 def test_leaves_truth_and_determinism(gpu, case):
@@ -121,6 +172,7 @@ def test_leaves_truth_and_determinism(gpu, case):
     k = R if tr else C
     q, s, v = _q8.random_inputs(case)
     m, sc, vv, out = build_case(gpu, case, q, s, v)
+    dirty_workspace(gpu, case, (m, sc, vv, out))  # (a cut case: NaN in every partial it should write)
     gpu.take_path()
     run(gpu, tr, G, out, m, sc, vv)
     path = gpu.take_path()
@@ -142,6 +194,7 @@ def test_leaves_truth_and_determinism(gpu, case):
     r = _q8.assert_within_gate(got, truth, k, sabs, name)
     print(f"  worst err / gate = {r:.3g}")
     # 6: the same bits again
+    dirty_workspace(gpu, case, (m, sc, vv, out))
     out.poison()
     run(gpu, tr, G, out, m, sc, vv)
     U.assert_bits_equal(out.read(name), got, f"{name}: second call")
@@ -156,7 +209,10 @@ def test_exact_operands(gpu, case):
     q, s, v = _q8.exact_inputs(case)
     assert (q == -128).any() and _q8.exactness_condition(q, s, v, tr) < 2.0 ** 24
     m, sc, vv, out = build_case(gpu, case, q, s, v)
+    dirty_workspace(gpu, case, (m, sc, vv, out))
+    gpu.take_path()
     run(gpu, tr, G, out, m, sc, vv)
+    assert (" gemv_q8/combine,ns=" in gpu.take_path()) == name.endswith("_split"), name
     truth, _ = _q8.truth64(q, s, v, G, tr)
     want = truth.astype(np.float32)
     assert np.array_equal(want.astype(np.float64), truth)
@@ -485,21 +541,25 @@ def masked():
     inst.sync()
 
 
-REPLAY = [c for c in _q8.CASES if c[0] in ("t_trips", "t_8rhs", "t_split", "t4_8rhs", "t4_split", "n_rows_plus", "n_split", "any_t", "any_n")]
+REPLAY = [c for c in _q8.CASES if c[0] in ("t_trips", "t_8rhs", "t_split", "t4_8rhs", "t4_split", "n_rows_plus", "n_split", "any_t", "any_n", "t_3rhs_split", "t_2mats_split",
+                                           "t4_3rhs_split", "t4_2mats_split", "n_3rhs_split", "n_2mats_split")]
 
 
 @pytest.mark.parametrize("where", ["whole", "masked"])
 def test_recorded_and_masked(gpu, masked, where):
-    """Eager, then recorded once and replayed twice into a re-poisoned output: the eager bits each time. On the whole chip and on a CU-masked context (248 CUs: the
+    """Eager, then recorded once and replayed twice into a re-poisoned output (a cut case: on a workspace dirtied before the eager call and before each replay): the
+    eager bits each time. On the whole chip and on a CU-masked context (248 CUs: the
     plan reads the context's CU count), where the truth gate and determinism hold."""
     inst = gpu if where == "whole" else masked
     for case in REPLAY:
         name, tr, R, C, nrhs, Z, G = case[:7]
         q, s, v = _q8.random_inputs(case, salt=3)
         m, sc, vv, out = build_case(inst, case, q, s, v)
+        dirty_workspace(inst, case, (m, sc, vv, out))
         inst.take_path()
         run(inst, tr, G, out, m, sc, vv)
         log = inst.take_path()
+        assert (" gemv_q8/combine,ns=" in log) == name.endswith("_split"), (name, log)
         eager = out.read(name)
         truth, sabs = _q8.truth64(q, s, v, G, tr)
         _q8.assert_within_gate(eager, truth, R if tr else C, sabs, f"{name} {where}")
@@ -511,6 +571,7 @@ def test_recorded_and_masked(gpu, masked, where):
             cb = enc.finish()
         assert inst.take_path() == log
         for rep in range(2):
+            dirty_workspace(inst, case, (m, sc, vv, out))
             out.poison()
             inst.queue().submit([cb])
             U.assert_bits_equal(out.read(name), eager, f"{name} {where}: replay {rep}")
