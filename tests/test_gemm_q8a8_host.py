@@ -69,11 +69,18 @@ def test_refusals_in_their_order():
 
 
 def test_other_entry_points_are_untouched_by_the_new_one():
-    """wg_gemm_q8 keeps its own checks and kernels: the new function shares helpers, not code paths, and the new unit launches a combine kernel of its own."""
+    """wg_gemm_q8 keeps its own checks and kernels: the new function shares helpers, not code paths. Its unit defines no combine kernel and launches no other family's
+    kernels: the partials of a cut go through the quantized families' one combine pass (tests/test_quant_plan_parent.py and the bit-exact GPU tests hold what that
+    sharing must not change)."""
+    import re
     body = _body()
     assert "wgk_gemm_q8(" not in body and "gemm_q8_plan(" not in body and "gemm_launch" not in body
     unit = open(os.path.join(ROOT, "wgmath_amd", "csrc", "gemm_q8a8.hip")).read()
-    assert "gemm_q8a8_combine_kernel" in unit and "hipLaunchKernelGGL(gemm_q8_combine_kernel" not in unit
+    kernels = re.findall(r"__global__[^;{]*?void\s+(\w+)\s*\(", unit)
+    assert kernels and not [k for k in kernels if "combine" in k], kernels
+    launched = set(re.findall(r"hipLaunchKernelGGL\(\(?(\w+)", unit))
+    assert launched and launched <= set(kernels), launched - set(kernels)
+    assert "wgk_q_combine(ctx, true, " in unit
     with pytest.raises(TypeError):
         wg.wgcore.wg_dtype(np.int8)
 

@@ -39,8 +39,8 @@
 //  any: one element-by-element kernel for every view the streaming kernel cannot address (gemm_q4_plan.hip: streams()): a wave per output walking the columns, a
 //     lane takes a byte -- two weights -- per step: w = s * q, acc = fmaf(w, (float)x, acc), even row first. Correct, not fast; everything is read where it lies.
 //
-// A cut writes f32 partials [z][split][n][outputs] into the context's workspace; gemm_q4_combine_kernel (this unit's own) adds them in a fixed order (no atomics:
-// same bits every call). Outputs past the last one re-read the last one, columns past N the last column; neither is stored.
+// A cut writes f32 partials [z][split][n][outputs] into the context's workspace; the quantized families' one combine pass (quant_combine.hip: wgk_q_combine) adds them
+// in a fixed order (no atomics: same bits every call). Outputs past the last one re-read the last one, columns past N the last column; neither is stored.
 #include "wg_internal.hpp"
 #include "gemm_q4_plan.hpp"
 
@@ -48,7 +48,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kLoads = 4;                          // 16-byte loads of weights in flight per lane
-constexpr uint32_t kDouble = 2u * kGQ4Step;        // rows a wave-load covers: a double step
+constexpr uint32_t kDouble = 2u * kGQStep;         // rows a wave-load covers: a double step
 constexpr uint32_t kTrip = kDouble * kLoads;       // 256 rows
 
 struct GQ4Args {
@@ -141,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void gemm_q4_mfma_kernel(GQ4Args a) {
     typedef typename E::v8 v8;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t c = lane & 31u, h = lane >> 5;
-    const uint64_t o0 = ((uint64_t)blockIdx.x * kGQ4Waves + wave) * kGQ4WaveOut;
+    const uint64_t o0 = ((uint64_t)blockIdx.x * kGQWaves + wave) * kGQWaveOut;
     if (o0 >= a.outputs) return; // whole waves leave; there is no barrier below
     const uint32_t z = blockIdx.z / a.passes, n0 = (blockIdx.z % a.passes) * (32u * T);
     const uint32_t r_begin = blockIdx.y * a.k_per_split;
@@ -189,7 +189,7 @@ __global__ __launch_bounds__(kThreads) void gemm_q4_mfma_kernel(GQ4Args a) {
     // the scale of the step the load cursor stands on, and whether that step ends its group; moves the cursor on
     auto next_group = [&](float &s, bool &ends) {
         s = sp[g];
-        gleft -= kGQ4Step;
+        gleft -= kGQStep;
         ends = gleft == 0u;
         if (ends) { gleft = a.g_eff; ++g; }
     };
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void gemm_q4_mfma_kernel(GQ4Args a) {
             const wg_u4 e = exchange(q[u]);
             const uint32_t r = r0 + kDouble * u;
             step(r, e[0], e[1], s[2 * u], ends[2 * u]);
-            step(r + kGQ4Step, e[2], e[3], s[2 * u + 1], ends[2 * u + 1] || (uint64_t)r + kDouble >= r_end);
+            step(r + kGQStep, e[2], e[3], s[2 * u + 1], ends[2 * u + 1] || (uint64_t)r + kDouble >= r_end);
         }
     }
     if (r0 < r_end) { // what is left (< one trip): one guarded trip. k % 32 == 0: a step is all in or all out; a double step may have its first step only, and then
@@ -223,9 +223,9 @@ __global__ __launch_bounds__(kThreads) void gemm_q4_mfma_kernel(GQ4Args a) {
             const uint64_t r = (uint64_t)r0 + kDouble * u; // (64 bits: a tail next to 2^32 rows must not wrap into range)
             q[u] = (wg_u4){ 0u, 0u, 0u, 0u };
             if (r < r_end) {
-                if (r + kGQ4Step * h < r_end) q[u] = ld_piece(mp + r / 2u);
+                if (r + kGQStep * h < r_end) q[u] = ld_piece(mp + r / 2u);
                 next_group(s[2 * u], ends[2 * u]);
-                if (r + kGQ4Step < r_end) next_group(s[2 * u + 1], ends[2 * u + 1]);
+                if (r + kGQStep < r_end) next_group(s[2 * u + 1], ends[2 * u + 1]);
             }
         }
 #pragma unroll
@@ -233,8 +233,8 @@ __global__ __launch_bounds__(kThreads) void gemm_q4_mfma_kernel(GQ4Args a) {
             const uint64_t r = (uint64_t)r0 + kDouble * u;
             if (r < r_end) { // (uniform)
                 const wg_u4 e = exchange(q[u]);
-                step((uint32_t)r, e[0], e[1], s[2 * u], ends[2 * u] || r + kGQ4Step >= r_end);
-                if (r + kGQ4Step < r_end) step((uint32_t)r + kGQ4Step, e[2], e[3], s[2 * u + 1], ends[2 * u + 1] || r + kDouble >= r_end);
+                step((uint32_t)r, e[0], e[1], s[2 * u], ends[2 * u] || r + kGQStep >= r_end);
+                if (r + kGQStep < r_end) step((uint32_t)r + kGQStep, e[2], e[3], s[2 * u + 1], ends[2 * u + 1] || r + kDouble >= r_end);
             }
         }
     }
@@ -250,34 +250,6 @@ __global__ __launch_bounds__(kThreads) void gemm_q4_mfma_kernel(GQ4Args a) {
                 if (col < a.n) dp[(uint64_t)col * a.ld_dst] = acc[t][i];
             }
     }
-}
-
-// out[o, n] = sum over the splits in a FIXED order. partial layout: [z][s][n][outputs] dense. A workgroup covers 64 outputs x 4 split lanes (its waves): wave w adds
-// splits w, w + 4, ... ascending with 8 independent loads in flight, then the 4 waves are added ascending through the LDS. grid = (ceil(outputs / 64), n, mats)
-__global__ __launch_bounds__(kThreads) void gemm_q4_combine_kernel(const float *__restrict__ part, uint32_t nsplit, uint32_t outputs, uint32_t n, float *__restrict__ out,
-                                                                    uint32_t ld_out, uint64_t out_batch) {
-    __shared__ float red[3][64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t r = (uint64_t)blockIdx.x * 64u + lane;
-    const uint32_t y = blockIdx.y, z = blockIdx.z;
-    const bool ok = r < outputs;
-    const uint64_t split_stride = (uint64_t)n * outputs;
-    float s = 0.f;
-    if (ok) {
-        const float *p = part + (uint64_t)z * nsplit * split_stride + (uint64_t)y * outputs + r;
-        uint32_t i = wave;
-        for (; i + 28u < nsplit; i += 32u) {
-            float q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = p[(uint64_t)(i + 4u * u) * split_stride];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += q[u];
-        }
-        for (; i < nsplit; i += 4u) s += p[(uint64_t)i * split_stride];
-    }
-    if (wave > 0) red[wave - 1][lane] = s;
-    __syncthreads();
-    if (wave == 0 && ok) out[z * out_batch + (uint64_t)y * ld_out + r] = ((s + red[0][lane]) + red[1][lane]) + red[2][lane];
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -320,21 +292,12 @@ int wgk_gemm_q4(wg_ctx *ctx, const wg_gemm_q4_plan &p, bool bf16, uint32_t group
     a.x = (const uint16_t *)x.ptr; a.ldx = x.ld; a.x_batch = x.batch;
     a.outputs = outputs; a.k = k; a.n = n; a.passes = p.col_passes; a.k_per_split = p.k_per_split;
     a.group_rows = group_rows;
-    const bool one_group = group_rows >= k;
-    a.g_eff = one_group ? 0u - kGQ4Step : group_rows;
-    a.groups_per_split = one_group ? 0u : p.k_per_split / group_rows;
-    a.g_shift = one_group ? 32u : (group_rows & (group_rows - 1u)) == 0u ? (uint32_t)__builtin_ctz(group_rows) : 255u;
-    if (p.nsplit > 1) { // f32 partials in the context's workspace (it cannot grow inside a recording)
-        void *ws = nullptr;
-        if (int rc = wg_ctx_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
-        a.dst = (float *)ws;
-        a.ld_dst = outputs;
-        a.dst_split = (uint64_t)n * outputs;
-        a.dst_batch = (uint64_t)p.nsplit * n * outputs;
-    } else {
-        a.dst = out; a.ld_dst = out_ld; a.dst_split = 0; a.dst_batch = out_batch;
-    }
-    const GemmQ4Tags tags = gemm_q4_tags(p, bf16);
+    const wgk_q_groups g = wgk_q_group_args(group_rows, k, p.k_per_split, kGQStep);
+    a.g_eff = g.g_eff; a.groups_per_split = g.groups_per_split; a.g_shift = g.g_shift;
+    wgk_q_dst d;
+    if (int rc = wgk_q_destination(ctx, p.nsplit, p.workspace_bytes, outputs, n, out, out_ld, out_batch, &d)) return rc;
+    a.dst = d.dst; a.ld_dst = d.ld_dst; a.dst_batch = d.dst_batch; a.dst_split = d.dst_split;
+    const wgq::Tags tags = gemm_q4_tags(p, bf16);
     const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
     wg_path(ctx, "%s", tags.tag[0]);
     if (p.leaf == WG_GEMM_Q4_MFMA) {
@@ -352,9 +315,7 @@ int wgk_gemm_q4(wg_ctx *ctx, const wg_gemm_q4_plan &p, bool bf16, uint32_t group
     WG_HIP_TRY(hipGetLastError());
     if (p.nsplit > 1) {
         wg_path(ctx, "%s", tags.tag[1]);
-        hipLaunchKernelGGL(gemm_q4_combine_kernel, dim3((outputs + 63u) / 64u, n, nmats), dim3(kThreads), 0, ctx->stream, (const float *)a.dst, p.nsplit, outputs, n, out,
-                           out_ld, out_batch);
-        WG_HIP_TRY(hipGetLastError());
+        if (int rc = wgk_q_combine(ctx, true, a.dst, p.nsplit, outputs, n, nmats, out, out_ld, out_batch)) return rc;
     }
     return WG_OK;
 }

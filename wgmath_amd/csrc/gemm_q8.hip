@@ -17,7 +17,8 @@
 //  any: one element-by-element kernel for every view the streaming kernel cannot address (gemm_q8_plan.hip: streams()): w = s * q, acc = fmaf(w, (float)x, acc), a
 //     wave per output walking the columns. Correct, not fast; everything is read where it lies.
 //
-// A cut writes f32 partials [z][split][n][outputs] into the context's workspace; gemm_q8_combine_kernel adds them in a fixed order (no atomics: same bits every call).
+// A cut writes f32 partials [z][split][n][outputs] into the context's workspace; the quantized families' one combine pass (quant_combine.hip: wgk_q_combine) adds them
+// in a fixed order (no atomics: same bits every call).
 //
 // The conversion (the disassembly of the four instances): f16 -- the magic-number form, u = q ^ 0x80 placed under 0x6400 is the f16 value 1024 + u, and a packed
 // subtraction of 1152 leaves q exactly: per 4 weights one v_xor, two v_perm_b32 (or and/lshl/or pairs) and two v_pk_add_f16. bf16 -- sign-extend + v_cvt_f32_i32 (sdwa
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void gemm_q8_mfma_kernel(GQ8Args a) {
     typedef typename E::v8 v8;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t c = lane & 31u, h = lane >> 5;
-    const uint64_t o0 = ((uint64_t)blockIdx.x * kGQ8Waves + wave) * kGQ8WaveOut;
+    const uint64_t o0 = ((uint64_t)blockIdx.x * kGQWaves + wave) * kGQWaveOut;
     if (o0 >= a.outputs) return; // whole waves leave; there is no barrier below
     const uint32_t z = blockIdx.z / a.passes, n0 = (blockIdx.z % a.passes) * (32u * T);
     const uint32_t r_begin = blockIdx.y * a.k_per_split;
@@ -150,12 +151,12 @@ __global__ __launch_bounds__(kThreads) void gemm_q8_mfma_kernel(GQ8Args a) {
     // the scale of the step the load cursor stands on, and whether that step ends its group; moves the cursor on
     auto next_group = [&](float &s, bool &ends) {
         s = sp[g];
-        gleft -= kGQ8Step;
+        gleft -= kGQStep;
         ends = gleft == 0u;
         if (ends) { gleft = a.g_eff; ++g; }
     };
 
-    constexpr uint32_t kTrip = kGQ8Step * kLoads;
+    constexpr uint32_t kTrip = kGQStep * kLoads;
     uint32_t r0 = r_begin;
     for (; (uint64_t)r0 + kTrip <= r_end; r0 += kTrip) { // whole trips: kLoads pieces in flight per lane
         wg_i4 q[kLoads];
@@ -163,11 +164,11 @@ __global__ __launch_bounds__(kThreads) void gemm_q8_mfma_kernel(GQ8Args a) {
         bool ends[kLoads];
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
-            q[u] = ld_piece(mp + r0 + kGQ8Step * u);
+            q[u] = ld_piece(mp + r0 + kGQStep * u);
             next_group(s[u], ends[u]);
         }
 #pragma unroll
-        for (int u = 0; u < kLoads; ++u) step(r0 + kGQ8Step * u, q[u], s[u], ends[u] || (uint64_t)r0 + kGQ8Step * (u + 1) >= r_end);
+        for (int u = 0; u < kLoads; ++u) step(r0 + kGQStep * u, q[u], s[u], ends[u] || (uint64_t)r0 + kGQStep * (u + 1) >= r_end);
     }
     if (r0 < r_end) { // what is left (< one trip): one guarded trip; steps past the end are neither loaded nor added (k % 32 == 0: a step is all in or all out)
         wg_i4 q[kLoads];
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void gemm_q8_mfma_kernel(GQ8Args a) {
         bool ends[kLoads];
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
-            const uint64_t r = (uint64_t)r0 + kGQ8Step * u; // (64 bits: a tail next to 2^32 rows must not wrap into range)
+            const uint64_t r = (uint64_t)r0 + kGQStep * u; // (64 bits: a tail next to 2^32 rows must not wrap into range)
             if (r < r_end) {
                 q[u] = ld_piece(mp + r);
                 next_group(s[u], ends[u]);
@@ -183,8 +184,8 @@ __global__ __launch_bounds__(kThreads) void gemm_q8_mfma_kernel(GQ8Args a) {
         }
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
-            const uint64_t r = (uint64_t)r0 + kGQ8Step * u;
-            if (r < r_end) step((uint32_t)r, q[u], s[u], ends[u] || r + kGQ8Step >= r_end);
+            const uint64_t r = (uint64_t)r0 + kGQStep * u;
+            if (r < r_end) step((uint32_t)r, q[u], s[u], ends[u] || r + kGQStep >= r_end);
         }
     }
 
@@ -199,34 +200,6 @@ __global__ __launch_bounds__(kThreads) void gemm_q8_mfma_kernel(GQ8Args a) {
                 if (col < a.n) dp[(uint64_t)col * a.ld_dst] = acc[t][i];
             }
     }
-}
-
-// out[o, n] = sum over the splits in a FIXED order. partial layout: [z][s][n][outputs] dense. A workgroup covers 64 outputs x 4 split lanes (its waves): wave w adds
-// splits w, w + 4, ... ascending with 8 independent loads in flight, then the 4 waves are added ascending through the LDS. grid = (ceil(outputs / 64), n, mats)
-__global__ __launch_bounds__(kThreads) void gemm_q8_combine_kernel(const float *__restrict__ part, uint32_t nsplit, uint32_t outputs, uint32_t n, float *__restrict__ out,
-                                                                    uint32_t ld_out, uint64_t out_batch) {
-    __shared__ float red[3][64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t r = (uint64_t)blockIdx.x * 64u + lane;
-    const uint32_t y = blockIdx.y, z = blockIdx.z;
-    const bool ok = r < outputs;
-    const uint64_t split_stride = (uint64_t)n * outputs;
-    float s = 0.f;
-    if (ok) {
-        const float *p = part + (uint64_t)z * nsplit * split_stride + (uint64_t)y * outputs + r;
-        uint32_t i = wave;
-        for (; i + 28u < nsplit; i += 32u) {
-            float q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = p[(uint64_t)(i + 4u * u) * split_stride];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += q[u];
-        }
-        for (; i < nsplit; i += 4u) s += p[(uint64_t)i * split_stride];
-    }
-    if (wave > 0) red[wave - 1][lane] = s;
-    __syncthreads();
-    if (wave == 0 && ok) out[z * out_batch + (uint64_t)y * ld_out + r] = ((s + red[0][lane]) + red[1][lane]) + red[2][lane];
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -265,21 +238,12 @@ int wgk_gemm_q8(wg_ctx *ctx, const wg_gemm_q8_plan &p, bool bf16, uint32_t group
     a.x = (const uint16_t *)x.ptr; a.ldx = x.ld; a.x_batch = x.batch;
     a.outputs = outputs; a.k = k; a.n = n; a.passes = p.col_passes; a.k_per_split = p.k_per_split;
     a.group_rows = group_rows;
-    const bool one_group = group_rows >= k;
-    a.g_eff = one_group ? 0u - kGQ8Step : group_rows;
-    a.groups_per_split = one_group ? 0u : p.k_per_split / group_rows;
-    a.g_shift = one_group ? 32u : (group_rows & (group_rows - 1u)) == 0u ? (uint32_t)__builtin_ctz(group_rows) : 255u;
-    if (p.nsplit > 1) { // f32 partials in the context's workspace (it cannot grow inside a recording)
-        void *ws = nullptr;
-        if (int rc = wg_ctx_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
-        a.dst = (float *)ws;
-        a.ld_dst = outputs;
-        a.dst_split = (uint64_t)n * outputs;
-        a.dst_batch = (uint64_t)p.nsplit * n * outputs;
-    } else {
-        a.dst = out; a.ld_dst = out_ld; a.dst_split = 0; a.dst_batch = out_batch;
-    }
-    const GemmQ8Tags tags = gemm_q8_tags(p, bf16);
+    const wgk_q_groups g = wgk_q_group_args(group_rows, k, p.k_per_split, kGQStep);
+    a.g_eff = g.g_eff; a.groups_per_split = g.groups_per_split; a.g_shift = g.g_shift;
+    wgk_q_dst d;
+    if (int rc = wgk_q_destination(ctx, p.nsplit, p.workspace_bytes, outputs, n, out, out_ld, out_batch, &d)) return rc;
+    a.dst = d.dst; a.ld_dst = d.ld_dst; a.dst_batch = d.dst_batch; a.dst_split = d.dst_split;
+    const wgq::Tags tags = gemm_q8_tags(p, bf16);
     const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
     wg_path(ctx, "%s", tags.tag[0]);
     if (p.leaf == WG_GEMM_Q8_MFMA) {
@@ -297,9 +261,7 @@ int wgk_gemm_q8(wg_ctx *ctx, const wg_gemm_q8_plan &p, bool bf16, uint32_t group
     WG_HIP_TRY(hipGetLastError());
     if (p.nsplit > 1) {
         wg_path(ctx, "%s", tags.tag[1]);
-        hipLaunchKernelGGL(gemm_q8_combine_kernel, dim3((outputs + 63u) / 64u, n, nmats), dim3(kThreads), 0, ctx->stream, (const float *)a.dst, p.nsplit, outputs, n, out,
-                           out_ld, out_batch);
-        WG_HIP_TRY(hipGetLastError());
+        if (int rc = wgk_q_combine(ctx, true, a.dst, p.nsplit, outputs, n, nmats, out, out_ld, out_batch)) return rc;
     }
     return WG_OK;
 }

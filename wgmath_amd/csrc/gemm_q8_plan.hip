@@ -1,33 +1,20 @@
-// The planner of wg_gemm_q8's launcher: which kernel a call takes, with what column tile, cut of the contraction, grid and workspace (gemm_q8_plan.hpp).
+// The planner of wg_gemm_q8's launcher: which kernel a call takes, with what column tile, cut of the contraction, grid and workspace (gemm_q8_plan.hpp). The body is
+// the Gemm families' shared one (quant_plan_common.hpp: wgq::gemm_plan); what is wg_gemm_q8's own is here: what its MFMA kernel can address, the unit of the cut, the tags.
 // Host arithmetic on sizes, strides, addresses modulo 16 and the CU count. No kernel, no device call, no context -- the launcher (gemm_q8.hip) executes the plan,
 // tests read it through wg_debug_gemm_q8_plan and tests/cpp/gemm_q8_plan_check.cpp links this unit alone (under the host sanitizers).
 #include "gemm_q8_plan.hpp"
-
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 
 int wg_set_error(int status, const char *fmt, ...) __attribute__((format(printf, 2, 3))); // (runtime.hip)
 
 namespace {
 
-inline uint32_t ceil_div(uint32_t a, uint32_t b) { return a / b + (a % b != 0); }
-
-wg_gemm_q8_plan no_launch(wg_gemm_q8_plan p, int status, const char *fmt, ...) {
-    p.leaf = WG_GEMM_Q8_UNSUPPORTED;
-    p.status = status;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(p.message, sizeof p.message, fmt, ap);
-    va_end(ap);
-    return p;
-}
+constexpr wgq::GemmLeaves kLeaves = { WG_GEMM_Q8_NOTHING, WG_GEMM_Q8_UNSUPPORTED, WG_GEMM_Q8_MFMA, WG_GEMM_Q8_ANY };
 
 // what the streaming kernel needs: whole 32-row steps that never straddle a group, and 16-byte loads of `m` (16 weights) and of `x` (8 elements) at 16-byte
 // addresses -- every column, every matrix. `out` is stored one float at a time: any view.
 bool streams(const wg_gemm_q8_query &q) {
-    if (q.k == 0 || q.k % kGQ8Step) return false; // (k % 16 == 0 alone is not taken: no zero-filled half step; k == 0 writes zeros element by element)
-    if (q.group_rows < q.k && q.group_rows % kGQ8Step) return false;
+    if (q.k == 0 || q.k % kGQStep) return false; // (k % 16 == 0 alone is not taken: no zero-filled half step; k == 0 writes zeros element by element)
+    if (q.group_rows < q.k && q.group_rows % kGQStep) return false;
     if (q.m_addr16 % 16 || (q.outputs > 1 && q.ldm % 16) || (q.mats > 1 && q.m_batch % 16)) return false;
     if (q.x_addr16 % 16 || (q.n > 1 && q.ldx % 8) || (q.mats > 1 && q.x_batch % 8)) return false;
     return true;
@@ -36,71 +23,16 @@ bool streams(const wg_gemm_q8_query &q) {
 } // namespace
 
 wg_gemm_q8_plan gemm_q8_plan(const wg_gemm_q8_query &q) {
-    wg_gemm_q8_plan p = {};
-    p.nsplit = 1; p.k_per_split = q.k; p.col_tiles = 0; p.col_passes = 1; p.block = 256;
-    if (q.outputs == 0 || q.n == 0 || q.mats == 0) { p.leaf = WG_GEMM_Q8_NOTHING; return p; }
-    const uint32_t cus = q.cus ? q.cus : 1u;
-
-    if (!streams(q)) { // element by element: a wave per output walks the columns; no cut, no workspace; k == 0 writes zeros
-        if (q.mats > 65535u) return no_launch(p, WG_ERR_UNSUPPORTED, "Gemm: nmats = %u exceeds 65535", q.mats);
-        p.leaf = WG_GEMM_Q8_ANY;
-        p.block = 64;
-        p.out_per_block = 1;
-        p.grid[0] = q.outputs; p.grid[1] = 1; p.grid[2] = q.mats;
-        return p;
-    }
-
-    p.leaf = WG_GEMM_Q8_MFMA;
-    // the column tile of a wave: one 32 x 32 accumulator tile up to 32 columns, two beyond; N past 64 streams the weights once per pass of 64 columns
-    p.col_tiles = q.n <= 32u ? 2u : kGQ8MaxColTiles;
-    p.col_passes = ceil_div(q.n, 16u * p.col_tiles);
-    const uint64_t gz64 = (uint64_t)q.mats * p.col_passes;
-    if (gz64 > 65535) return no_launch(p, WG_ERR_UNSUPPORTED, "Gemm: nmats * column passes = %llu exceeds 65535", (unsigned long long)gz64);
-    const uint32_t gz = (uint32_t)gz64;
-    p.out_per_block = kGQ8WaveOut * kGQ8Waves;
-    p.grid[0] = ceil_div(q.outputs, p.out_per_block);
-    // the cut of the contraction: kGQ8BlocksPerCU workgroups per CU, never below a floor of work per split; every boundary a multiple of 32 and, where the
-    // groups are shorter than k, of group_rows (a group is never cut: its scale enters once, behind its own MFMA chain)
-    const uint32_t unit = q.group_rows < q.k ? q.group_rows : kGQ8Step;
-    const uint64_t blocks = (uint64_t)p.grid[0] * gz, want_blocks = (uint64_t)kGQ8BlocksPerCU * cus;
-    uint32_t want = blocks >= want_blocks ? 1u : (uint32_t)((want_blocks + blocks - 1) / blocks);
-    const uint32_t max_split = q.k / kGQ8FloorK ? q.k / kGQ8FloorK : 1u; // (rounded down: no split falls below the floor)
-    if (want > max_split) want = max_split;
-    if (want > 65535u) want = 65535u;
-    if (q.n > 65535u) want = 1u; // (the combine pass puts the columns on grid.y; that many fill the chip unsplit)
-    if (want > 1u) {
-        const uint64_t per = (uint64_t)ceil_div(ceil_div(q.k, want), unit) * unit;
-        if (per < q.k) {
-            p.k_per_split = (uint32_t)per;
-            p.nsplit = ceil_div(q.k, p.k_per_split);
-        }
-    }
-    p.grid[1] = p.nsplit; p.grid[2] = gz;
-    if (p.nsplit > 1) p.workspace_bytes = (uint64_t)q.mats * p.nsplit * q.n * q.outputs * sizeof(float);
-    return p;
+    // every boundary of the cut a multiple of 32 and, where the groups are shorter than k, of group_rows
+    return wgq::gemm_plan<wg_gemm_q8_plan>(q, kLeaves, streams(q), q.group_rows < q.k ? q.group_rows : kGQStep);
 }
 
-GemmQ8Tags gemm_q8_tags(const wg_gemm_q8_plan &p, bool x_bf16) {
-    GemmQ8Tags t = {};
-    switch (p.leaf) {
-    case WG_GEMM_Q8_MFMA: snprintf(t.tag[t.n++], sizeof t.tag[0], "gemm_q8/mfma,%s,nt=%u,ns=%u", x_bf16 ? "bf16" : "f16", p.col_tiles, p.nsplit); break;
-    case WG_GEMM_Q8_ANY: snprintf(t.tag[t.n++], sizeof t.tag[0], "gemm_q8/any"); break;
-    default: return t;
-    }
-    if (p.nsplit > 1) snprintf(t.tag[t.n++], sizeof t.tag[0], "gemm_q8/combine,ns=%u", p.nsplit);
-    return t;
-}
+wgq::Tags gemm_q8_tags(const wg_gemm_q8_plan &p, bool x_bf16) { return wgq::gemm_tags(p, kLeaves, "gemm_q8", x_bf16 ? "bf16" : "f16"); }
 
 // Host-side view of gemm_q8_plan (tests/test_gemm_q8_plan_host.py; no context, no device): the plan of a query and the launch log such a call leaves.
 extern "C" int wg_debug_gemm_q8_plan(const wg_gemm_q8_query *query, wg_gemm_q8_plan *plan, char *tags, size_t cap) {
     if (!query || !plan || (cap && !tags)) return wg_set_error(WG_ERR_INVALID_ARG, "wg_debug_gemm_q8_plan: NULL argument");
     *plan = gemm_q8_plan(*query);
-    std::string log;
-    const GemmQ8Tags t = gemm_q8_tags(*plan, query->x_bf16 != 0);
-    for (int i = 0; i < t.n; ++i) { // joined as wg_path joins them
-        if (!log.empty()) log += ' ';
-        log += t.tag[i];
-    }
-    if (cap) snprintf(tags, cap, "%s", log.c_str());
+    wgq::join_tags(gemm_q8_tags(*plan, query->x_bf16 != 0), tags, cap);
     return WG_OK;
 }

@@ -4,21 +4,9 @@
 #pragma once
 #include <cstdint>
 
-#include "../../include/wgebra_hip.h"
-
-// the constants the kernel and the plan share
-constexpr uint32_t kGQ8Step = 32;         // rows of one step: two 32x32x16 MFMAs on a lane's 16-byte piece; the unit of group_rows and of every cut on the MFMA leaf
-constexpr uint32_t kGQ8WaveOut = 32;      // outputs a wave owns
-constexpr uint32_t kGQ8Waves = 4;         // waves per 256-thread workgroup, on adjacent 32-output blocks of the same split
-constexpr uint32_t kGQ8MaxColTiles = 4;   // 16-column accumulator tiles a wave carries at most: 64 columns per pass over the weights
-constexpr uint32_t kGQ8FloorK = 512;      // rows per split at least (16 steps)
-constexpr uint32_t kGQ8BlocksPerCU = 4;   // workgroups per CU the cut aims at (16 waves: 4 per SIMD)
+#include "quant_plan_common.hpp" // kGQStep and the other constants the kernel and the plan share
 
 wg_gemm_q8_plan gemm_q8_plan(const wg_gemm_q8_query &q);
 
 // The launch-log tags (wg_path) of a plan's launches, in launch order: the launcher logs exactly these.
-struct GemmQ8Tags {
-    int n;
-    char tag[2][48];
-};
-GemmQ8Tags gemm_q8_tags(const wg_gemm_q8_plan &p, bool x_bf16);
+wgq::Tags gemm_q8_tags(const wg_gemm_q8_plan &p, bool x_bf16);

@@ -21,8 +21,8 @@
 //  any: one element-by-element kernel for every view the streaming kernel cannot address (gemm_q8a8_plan.hip: streams()): a wave per output walks the columns and the
 //     chains; the lanes share a chain's rows, their int32 sums are added across the wave (integers: the order does not matter), then the same two f32 operations.
 //
-// A cut writes f32 partials [z][split][n][outputs] into the context's workspace; gemm_q8a8_combine_kernel (gemm_q8_combine_kernel's copy: no wg_gemm_q8 launch
-// changes) adds them in its fixed order (no atomics: same bits every call).
+// A cut writes f32 partials [z][split][n][outputs] into the context's workspace; the quantized families' one combine pass (quant_combine.hip: wgk_q_combine) adds them
+// in a fixed order (no atomics: same bits every call).
 #include "wg_internal.hpp"
 #include "gemm_q8a8_plan.hpp"
 
@@ -60,7 +60,7 @@ template <int T>
 __global__ __launch_bounds__(kThreads) void gemm_q8a8_mfma_kernel(GQ8A8Args a) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t c = lane & 31u, h = lane >> 5;
-    const uint64_t o0 = ((uint64_t)blockIdx.x * kGQ8A8Waves + wave) * kGQ8A8WaveOut;
+    const uint64_t o0 = ((uint64_t)blockIdx.x * kGQWaves + wave) * kGQWaveOut;
     if (o0 >= a.outputs) return; // whole waves leave; there is no barrier below
     const uint32_t z = blockIdx.z / a.passes, n0 = (blockIdx.z % a.passes) * (32u * T);
     const uint32_t r_begin = blockIdx.y * a.k_per_split;
@@ -114,7 +114,7 @@ __global__ __launch_bounds__(kThreads) void gemm_q8a8_mfma_kernel(GQ8A8Args a) {
     // the groups of the step the load cursor stands on, and whether that step ends its chain; moves the cursor on
     auto next_chain = [&](uint32_t &sw, uint32_t &sx, bool &ends) {
         sw = gw; sx = gx;
-        wpos += kGQ8A8Step; xpos += kGQ8A8Step; cpos += kGQ8A8Step;
+        wpos += kGQStep; xpos += kGQStep; cpos += kGQStep;
         const bool we = wpos == a.gw_eff, xe = xpos == a.gx_eff; // (an _eff of 0 is never reached: the positions stay below 2^32)
         ends = we || xe || cpos == kGQ8A8Chain;
         if (we) { wpos = 0; ++gw; }
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kThreads) void gemm_q8a8_mfma_kernel(GQ8A8Args a) {
         if (ends) cpos = 0; // (the coarser side's groups end where groups of the finer side end: the cap counts from the finer group's start)
     };
 
-    constexpr uint32_t kTrip = kGQ8A8Step * kLoads;
+    constexpr uint32_t kTrip = kGQStep * kLoads;
     uint32_t r0 = r_begin;
     for (; (uint64_t)r0 + kTrip <= r_end; r0 += kTrip) { // whole trips: kLoads pieces in flight per lane
         wg_i4 q[kLoads], xq[kLoads][T];
@@ -130,13 +130,13 @@ __global__ __launch_bounds__(kThreads) void gemm_q8a8_mfma_kernel(GQ8A8Args a) {
         bool ends[kLoads];
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
-            q[u] = ld_piece(mp + r0 + kGQ8A8Step * u);
+            q[u] = ld_piece(mp + r0 + kGQStep * u);
 #pragma unroll
-            for (int t = 0; t < T; ++t) xq[u][t] = *reinterpret_cast<const wg_i4 *>(xp[t] + r0 + kGQ8A8Step * u);
+            for (int t = 0; t < T; ++t) xq[u][t] = *reinterpret_cast<const wg_i4 *>(xp[t] + r0 + kGQStep * u);
             next_chain(sw[u], sx[u], ends[u]);
         }
 #pragma unroll
-        for (int u = 0; u < kLoads; ++u) step(xq[u], q[u], sw[u], sx[u], ends[u] || (uint64_t)r0 + kGQ8A8Step * (u + 1) >= r_end);
+        for (int u = 0; u < kLoads; ++u) step(xq[u], q[u], sw[u], sx[u], ends[u] || (uint64_t)r0 + kGQStep * (u + 1) >= r_end);
     }
     if (r0 < r_end) { // what is left (< one trip): one guarded trip; steps past the end are neither loaded nor added (k % 32 == 0: a step is all in or all out)
         wg_i4 q[kLoads], xq[kLoads][T];
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void gemm_q8a8_mfma_kernel(GQ8A8Args a) {
         bool ends[kLoads];
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
-            const uint64_t r = (uint64_t)r0 + kGQ8A8Step * u; // (64 bits: a tail next to 2^32 rows must not wrap into range)
+            const uint64_t r = (uint64_t)r0 + kGQStep * u; // (64 bits: a tail next to 2^32 rows must not wrap into range)
             if (r < r_end) {
                 q[u] = ld_piece(mp + r);
 #pragma unroll
@@ -154,8 +154,8 @@ __global__ __launch_bounds__(kThreads) void gemm_q8a8_mfma_kernel(GQ8A8Args a) {
         }
 #pragma unroll
         for (int u = 0; u < kLoads; ++u) {
-            const uint64_t r = (uint64_t)r0 + kGQ8A8Step * u;
-            if (r < r_end) step(xq[u], q[u], sw[u], sx[u], ends[u] || r + kGQ8A8Step >= r_end);
+            const uint64_t r = (uint64_t)r0 + kGQStep * u;
+            if (r < r_end) step(xq[u], q[u], sw[u], sx[u], ends[u] || r + kGQStep >= r_end);
         }
     }
 
@@ -170,35 +170,6 @@ __global__ __launch_bounds__(kThreads) void gemm_q8a8_mfma_kernel(GQ8A8Args a) {
                 if (col < a.n) dp[(uint64_t)col * a.ld_dst] = acc[t][i];
             }
     }
-}
-
-// out[o, n] = sum over the splits in a FIXED order (gemm_q8_combine_kernel's, restated here so that no wg_gemm_q8 launch changes). partial layout: [z][s][n][outputs]
-// dense. A workgroup covers 64 outputs x 4 split lanes (its waves): wave w adds splits w, w + 4, ... ascending with 8 independent loads in flight, then the 4 waves
-// are added ascending through the LDS. grid = (ceil(outputs / 64), n, mats)
-__global__ __launch_bounds__(kThreads) void gemm_q8a8_combine_kernel(const float *__restrict__ part, uint32_t nsplit, uint32_t outputs, uint32_t n, float *__restrict__ out,
-                                                                      uint32_t ld_out, uint64_t out_batch) {
-    __shared__ float red[3][64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t r = (uint64_t)blockIdx.x * 64u + lane;
-    const uint32_t y = blockIdx.y, z = blockIdx.z;
-    const bool ok = r < outputs;
-    const uint64_t split_stride = (uint64_t)n * outputs;
-    float s = 0.f;
-    if (ok) {
-        const float *p = part + (uint64_t)z * nsplit * split_stride + (uint64_t)y * outputs + r;
-        uint32_t i = wave;
-        for (; i + 28u < nsplit; i += 32u) {
-            float q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = p[(uint64_t)(i + 4u * u) * split_stride];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += q[u];
-        }
-        for (; i < nsplit; i += 4u) s += p[(uint64_t)i * split_stride];
-    }
-    if (wave > 0) red[wave - 1][lane] = s;
-    __syncthreads();
-    if (wave == 0 && ok) out[z * out_batch + (uint64_t)y * ld_out + r] = ((s + red[0][lane]) + red[1][lane]) + red[2][lane];
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -250,17 +221,10 @@ int wgk_gemm_q8a8(wg_ctx *ctx, const wg_gemm_q8a8_plan &p, uint32_t group_rows, 
     a.gx_eff = x_group_rows < k ? x_group_rows : 0u;
     const uint32_t gw = group_rows < k ? group_rows : k, gx = x_group_rows < k ? x_group_rows : k;
     a.fine = gw < gx ? gw : gx;
-    if (p.nsplit > 1) { // f32 partials in the context's workspace (it cannot grow inside a recording)
-        void *ws = nullptr;
-        if (int rc = wg_ctx_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
-        a.dst = (float *)ws;
-        a.ld_dst = outputs;
-        a.dst_split = (uint64_t)n * outputs;
-        a.dst_batch = (uint64_t)p.nsplit * n * outputs;
-    } else {
-        a.dst = out; a.ld_dst = out_ld; a.dst_split = 0; a.dst_batch = out_batch;
-    }
-    const GemmQ8A8Tags tags = gemm_q8a8_tags(p);
+    wgk_q_dst d;
+    if (int rc = wgk_q_destination(ctx, p.nsplit, p.workspace_bytes, outputs, n, out, out_ld, out_batch, &d)) return rc;
+    a.dst = d.dst; a.ld_dst = d.ld_dst; a.dst_batch = d.dst_batch; a.dst_split = d.dst_split;
+    const wgq::Tags tags = gemm_q8a8_tags(p);
     const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
     wg_path(ctx, "%s", tags.tag[0]);
     if (p.leaf == WG_GEMM_Q8A8_MFMA) {
@@ -272,9 +236,7 @@ int wgk_gemm_q8a8(wg_ctx *ctx, const wg_gemm_q8a8_plan &p, uint32_t group_rows, 
     WG_HIP_TRY(hipGetLastError());
     if (p.nsplit > 1) {
         wg_path(ctx, "%s", tags.tag[1]);
-        hipLaunchKernelGGL(gemm_q8a8_combine_kernel, dim3((outputs + 63u) / 64u, n, nmats), dim3(kThreads), 0, ctx->stream, (const float *)a.dst, p.nsplit, outputs, n, out,
-                           out_ld, out_batch);
-        WG_HIP_TRY(hipGetLastError());
+        if (int rc = wgk_q_combine(ctx, true, a.dst, p.nsplit, outputs, n, nmats, out, out_ld, out_batch)) return rc;
     }
     return WG_OK;
 }

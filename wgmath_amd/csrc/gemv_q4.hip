@@ -13,8 +13,8 @@
 //  any_t  one kernel for every view T cannot address (gemv_q4_plan.hip: streams()): a wave per column, a byte -- two weights -- per lane and step, w = s * q per
 //     element, acc = fmaf(w, v, acc). Correct, not fast; the matrix is read where it lies.
 //
-// A cut writes f32 partials [z][split][y][outputs] into the context's workspace; gemv_q4_combine_kernel adds them in a fixed order (four interleaved ascending sums,
-// then those four: no atomics: same bits every call) -- gemv_q8_combine_kernel's pass, a kernel of this unit so that nothing of wg_gemv_q8's changes.
+// A cut writes f32 partials [z][split][y][outputs] into the context's workspace; the quantized families' one combine pass (quant_combine.hip: wgk_q_combine) adds them
+// in a fixed order (four interleaved ascending sums, then those four: no atomics: same bits every call).
 //
 // The unpack. The budget: the f32 VALU issues 16 lanes per clock and SIMD, 64 per CU (a wave64 instruction takes 4 cycles; v_pk_fma_f32 does two FMAs in them), which
 // at 2.4 GHz against 0.82 of HBM is about 6 lane-instructions per matrix byte -- about 3 per WEIGHT here. (gemv_q8.hip's header counts 128 lanes per clock and CU,
@@ -215,34 +215,6 @@ __global__ __launch_bounds__(kThreads) void gemv_q4_t_kernel(Q4Args a) {
     }
 }
 
-// out[r] = sum over the splits in a FIXED order. partial layout: [z][s][y][rows_out] dense. A workgroup covers 64 outputs x 4 split lanes (its waves): wave w adds
-// splits w, w + 4, ... ascending with 8 independent loads in flight, then the 4 waves are added ascending through the LDS (gemv_q8_combine_kernel's pass).
-// grid = (ceil(rows_out / 64), nrhs, mats)
-__global__ __launch_bounds__(kThreads) void gemv_q4_combine_kernel(const float *__restrict__ part, uint32_t nsplit, uint32_t rows_out, uint32_t nrhs, float *__restrict__ out,
-                                                                    uint32_t ld_out, uint64_t out_batch) {
-    __shared__ float red[3][64];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t r = blockIdx.x * 64u + lane, y = blockIdx.y, z = blockIdx.z;
-    const bool ok = r < rows_out;
-    const uint64_t split_stride = (uint64_t)nrhs * rows_out;
-    float s = 0.f;
-    if (ok) {
-        const float *p = part + (uint64_t)z * nsplit * split_stride + (uint64_t)y * rows_out + r;
-        uint32_t i = wave;
-        for (; i + 28u < nsplit; i += 32u) {
-            float q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = p[(uint64_t)(i + 4u * u) * split_stride];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) s += q[u];
-        }
-        for (; i < nsplit; i += 4u) s += p[(uint64_t)i * split_stride];
-    }
-    if (wave > 0) red[wave - 1][lane] = s;
-    __syncthreads();
-    if (wave == 0 && ok) out[z * out_batch + (uint64_t)y * ld_out + r] = ((s + red[0][lane]) + red[1][lane]) + red[2][lane];
-}
-
 // ------------------------------------------------------------------------------------------------------
 // Any view, a byte (two weights) at a time: a wave per column, the right-hand sides of the group one after the other. grid = (columns, 1, mats * rhs groups), 64 threads
 // ------------------------------------------------------------------------------------------------------
@@ -282,18 +254,11 @@ int wgk_gemv_q4(wg_ctx *ctx, const wg_gemv_q4_plan &p, uint32_t group_rows, uint
     a.v = (const float *)v.ptr; a.ldv = v.ld; a.v_batch = v.batch;
     a.rows_out = rows_out; a.k = k; a.nrhs = nrhs; a.rhs_groups = p.rhs_groups; a.k_per_split = p.k_per_split;
     a.group_rows = group_rows;
-    a.g_shift = group_rows >= k ? 32u : (group_rows & (group_rows - 1u)) == 0u ? (uint32_t)__builtin_ctz(group_rows) : 255u;
-    if (p.nsplit > 1) { // f32 partials in the context's workspace (wgk_gemv's rule: it cannot grow inside a recording)
-        void *ws = nullptr;
-        if (int rc = wg_ctx_workspace(ctx, (size_t)p.workspace_bytes, &ws)) return rc;
-        a.dst = (float *)ws;
-        a.ld_dst = rows_out;
-        a.dst_split = (uint64_t)nrhs * rows_out;
-        a.dst_batch = (uint64_t)p.nsplit * nrhs * rows_out;
-    } else {
-        a.dst = out; a.ld_dst = out_ld; a.dst_split = 0; a.dst_batch = out_batch;
-    }
-    const GemvQ4Tags tags = gemv_q4_tags(p);
+    a.g_shift = wgk_q_group_shift(group_rows, k);
+    wgk_q_dst d;
+    if (int rc = wgk_q_destination(ctx, p.nsplit, p.workspace_bytes, rows_out, nrhs, out, out_ld, out_batch, &d)) return rc;
+    a.dst = d.dst; a.ld_dst = d.ld_dst; a.dst_batch = d.dst_batch; a.dst_split = d.dst_split;
+    const wgq::Tags tags = gemv_q4_tags(p);
     const dim3 grid(p.grid[0], p.grid[1], p.grid[2]), block(p.block);
     wg_path(ctx, "%s", tags.tag[0]);
     if (p.leaf == WG_GEMV_Q4_T) {
@@ -317,9 +282,7 @@ int wgk_gemv_q4(wg_ctx *ctx, const wg_gemv_q4_plan &p, uint32_t group_rows, uint
     WG_HIP_TRY(hipGetLastError());
     if (p.nsplit > 1) {
         wg_path(ctx, "%s", tags.tag[1]);
-        hipLaunchKernelGGL(gemv_q4_combine_kernel, dim3((rows_out + 63u) / 64u, nrhs, nmats), dim3(kThreads), 0, ctx->stream, (const float *)a.dst, p.nsplit, rows_out,
-                           nrhs, out, out_ld, out_batch);
-        WG_HIP_TRY(hipGetLastError());
+        if (int rc = wgk_q_combine(ctx, false, a.dst, p.nsplit, rows_out, nrhs, nmats, out, out_ld, out_batch)) return rc;
     }
     return WG_OK;
 }

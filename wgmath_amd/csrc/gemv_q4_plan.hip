@@ -3,25 +3,11 @@
 // tests read it through wg_debug_gemv_q4_plan and tests/cpp/gemv_q4_plan_check.cpp links this unit alone (under the host sanitizers).
 #include "gemv_q4_plan.hpp"
 
-#include <cstdarg>
-#include <cstdio>
-#include <string>
-
 int wg_set_error(int status, const char *fmt, ...) __attribute__((format(printf, 2, 3))); // (runtime.hip)
 
 namespace {
 
-inline uint32_t ceil_div(uint32_t a, uint32_t b) { return a / b + (a % b != 0); }
-
-wg_gemv_q4_plan no_launch(wg_gemv_q4_plan p, int status, const char *fmt, ...) {
-    p.leaf = WG_GEMV_Q4_UNSUPPORTED;
-    p.status = status;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(p.message, sizeof p.message, fmt, ap);
-    va_end(ap);
-    return p;
-}
+using wgq::ceil_div;
 
 // what the 16-byte accesses of the streaming kernel need: the matrix in whole 16-byte loads (32 weights) at 16-byte addresses -- every column, every matrix --, and
 // float4 accesses to `v` (32 entries beside every load; `scales` and `out` are reached one float at a time: any view)
@@ -37,14 +23,14 @@ wg_gemv_q4_plan gemv_q4_plan(const wg_gemv_q4_query &q) {
     wg_gemv_q4_plan p = {};
     p.nsplit = 1; p.rhs_tile = 1; p.rhs_groups = 1; p.block = 256; p.cols = 1;
     if (!q.trans)
-        return no_launch(p, WG_ERR_UNSUPPORTED, "Gemv: wg_gemv_q4 computes out = W^T v only (WG_GEMV_TR); wg_gemv_q8 computes out = W v, on int8 weights");
-    if (q.rows > 0x7fffffffu) return no_launch(p, WG_ERR_UNSUPPORTED, "Gemv: m has %u rows of bytes: k = 2 rows does not fit 32 bits", q.rows);
+        return wgq::no_launch(p, WG_GEMV_Q4_UNSUPPORTED, WG_ERR_UNSUPPORTED, "Gemv: wg_gemv_q4 computes out = W^T v only (WG_GEMV_TR); wg_gemv_q8 computes out = W v, on int8 weights");
+    if (q.rows > 0x7fffffffu) return wgq::no_launch(p, WG_GEMV_Q4_UNSUPPORTED, WG_ERR_UNSUPPORTED, "Gemv: m has %u rows of bytes: k = 2 rows does not fit 32 bits", q.rows);
     const uint32_t rows_out = q.cols, k = 2u * q.rows;
     p.k_per_split = k;
     if (rows_out == 0 || q.nrhs == 0 || q.mats == 0) { p.leaf = WG_GEMV_Q4_NOTHING; return p; }
     p.rhs_groups = ceil_div(q.nrhs, kQ4MaxRhs);
     const uint64_t gz64 = (uint64_t)q.mats * p.rhs_groups;
-    if (gz64 > 65535) return no_launch(p, WG_ERR_UNSUPPORTED, "Gemv: nmats * ceil(nrhs/8) = %llu exceeds 65535", (unsigned long long)gz64);
+    if (gz64 > 65535) return wgq::no_launch(p, WG_GEMV_Q4_UNSUPPORTED, WG_ERR_UNSUPPORTED, "Gemv: nmats * ceil(nrhs/8) = %llu exceeds 65535", (unsigned long long)gz64);
     const uint32_t gz = (uint32_t)gz64, cus = q.cus ? q.cus : 1u;
     // the register tile of a pass: the smallest of 1, 2, 4, 8 that holds min(nrhs, 8) right-hand sides (wgk_gemv's rule)
     const uint32_t per_group = q.nrhs < kQ4MaxRhs ? q.nrhs : kQ4MaxRhs;
@@ -73,29 +59,21 @@ wg_gemv_q4_plan gemv_q4_plan(const wg_gemv_q4_query &q) {
     // loads in flight per lane and column: 8 in all (4 from 3 right-hand sides on: the vectors' pieces live in registers beside the matrix's)
     p.loads = (p.rhs_tile <= 2 ? 8 : 4) / p.cols;
     p.grid[0] = ceil_div(rows_out, p.out_per_block);
-    const uint64_t blocks = (uint64_t)p.grid[0] * gz, want_blocks = (uint64_t)per_cu * cus;
-    uint32_t want = blocks >= want_blocks ? 1u : (uint32_t)((want_blocks + blocks - 1) / blocks);
-    const uint32_t max_split = k / floor_k ? k / floor_k : 1u; // (rounded down: no split falls below the floor)
-    if (want > max_split) want = max_split;
-    if (want > 65535u) want = 65535u;
-    if (q.nrhs > 65535u) want = 1u; // (the combine pass puts the right-hand sides on grid.y; that many fill the chip unsplit)
-    if (want > 1u) {
-        p.k_per_split = ceil_div(ceil_div(k, want), unit) * unit;
-        p.nsplit = ceil_div(k, p.k_per_split);
-    }
+    const wgq::Cut c = wgq::cut(k, unit, floor_k, (uint64_t)p.grid[0] * gz, (uint64_t)per_cu * cus, q.nrhs); // (the combine pass puts the right-hand sides on grid.y)
+    p.nsplit = c.nsplit; p.k_per_split = c.k_per_split;
     p.grid[1] = p.nsplit; p.grid[2] = gz;
     if (p.nsplit > 1) p.workspace_bytes = (uint64_t)q.mats * p.nsplit * q.nrhs * rows_out * sizeof(float);
     return p;
 }
 
-GemvQ4Tags gemv_q4_tags(const wg_gemv_q4_plan &p) {
-    GemvQ4Tags t = {};
+wgq::Tags gemv_q4_tags(const wg_gemv_q4_plan &p) {
+    wgq::Tags t = {};
     switch (p.leaf) {
     case WG_GEMV_Q4_T: snprintf(t.tag[t.n++], sizeof t.tag[0], "gemv_q4/t,nr=%u,u=%u,c=%u,ns=%u", p.rhs_tile, p.loads, p.cols, p.nsplit); break;
     case WG_GEMV_Q4_ANY_T: snprintf(t.tag[t.n++], sizeof t.tag[0], "gemv_q4/any_t"); break;
     default: return t;
     }
-    if (p.nsplit > 1) snprintf(t.tag[t.n++], sizeof t.tag[0], "gemv_q4/combine,ns=%u", p.nsplit);
+    wgq::tag_combine(t, "gemv_q4", p.nsplit);
     return t;
 }
 
@@ -103,12 +81,6 @@ GemvQ4Tags gemv_q4_tags(const wg_gemv_q4_plan &p) {
 extern "C" int wg_debug_gemv_q4_plan(const wg_gemv_q4_query *query, wg_gemv_q4_plan *plan, char *tags, size_t cap) {
     if (!query || !plan || (cap && !tags)) return wg_set_error(WG_ERR_INVALID_ARG, "wg_debug_gemv_q4_plan: NULL argument");
     *plan = gemv_q4_plan(*query);
-    std::string log;
-    const GemvQ4Tags t = gemv_q4_tags(*plan);
-    for (int i = 0; i < t.n; ++i) { // joined as wg_path joins them
-        if (!log.empty()) log += ' ';
-        log += t.tag[i];
-    }
-    if (cap) snprintf(tags, cap, "%s", log.c_str());
+    wgq::join_tags(gemv_q4_tags(*plan), tags, cap);
     return WG_OK;
 }

@@ -4,7 +4,7 @@
 #pragma once
 #include <cstdint>
 
-#include "../../include/wgebra_hip.h"
+#include "quant_plan_common.hpp"
 
 // the constants the kernel and the plan share, in LOGICAL rows (weights); a byte of the matrix holds two
 constexpr uint32_t kQ4Load = 32;         // weights per 16-byte load: k is a multiple of it on the streaming kernel, group_rows is a multiple of it or >= k
@@ -16,8 +16,4 @@ constexpr uint32_t kQ4MaxRhs = 8;        // right-hand sides per pass over the m
 wg_gemv_q4_plan gemv_q4_plan(const wg_gemv_q4_query &q);
 
 // The launch-log tags (wg_path) of a plan's launches, in launch order: the launcher logs exactly these.
-struct GemvQ4Tags {
-    int n;
-    char tag[2][48];
-};
-GemvQ4Tags gemv_q4_tags(const wg_gemv_q4_plan &p);
+wgq::Tags gemv_q4_tags(const wg_gemv_q4_plan &p);

@@ -4,7 +4,7 @@
 #pragma once
 #include <cstdint>
 
-#include "../../include/wgebra_hip.h"
+#include "quant_plan_common.hpp"
 
 // the constants the kernels and the plan share
 constexpr uint32_t kQ8Piece = 16;        // weights per 16-byte load: the unit of the scale in the streaming kernels, of group_rows and of every cut
@@ -16,8 +16,4 @@ constexpr uint32_t kQ8MaxRhs = 8;        // right-hand sides per pass over the m
 wg_gemv_q8_plan gemv_q8_plan(const wg_gemv_q8_query &q);
 
 // The launch-log tags (wg_path) of a plan's launches, in launch order: the launcher logs exactly these.
-struct GemvQ8Tags {
-    int n;
-    char tag[2][48];
-};
-GemvQ8Tags gemv_q8_tags(const wg_gemv_q8_plan &p);
+wgq::Tags gemv_q8_tags(const wg_gemv_q8_plan &p);

@@ -216,6 +216,34 @@ int wgk_gemm_q4(wg_ctx *ctx, const wg_gemm_q4_plan &p, bool bf16, uint32_t group
 // the plan is gemm_q8a8_plan.hip's; ld / batch strides count each operand's own elements.
 int wgk_gemm_q8a8(wg_ctx *ctx, const wg_gemm_q8a8_plan &p, uint32_t group_rows, uint32_t x_group_rows, uint32_t k, uint32_t outputs, uint32_t n, uint32_t nmats, float *out,
                   uint32_t out_ld, uint64_t out_batch, wgk_mat m, wgk_mat s, wgk_mat x, wgk_mat xs);
+// What those five launchers share (quant_combine.hip). The destination of a family's kernel: the output view, or under a cut (nsplit > 1) dense f32 partials
+// [z][split][y][outputs] in the context's workspace -- or the workspace's error; y_extent: the columns of x / the right-hand sides.
+struct wgk_q_dst {
+    float *dst;
+    uint32_t ld_dst;    // elements between columns / right-hand sides
+    uint64_t dst_batch; // ... between matrices
+    uint64_t dst_split; // ... between splits (partials only)
+};
+int wgk_q_destination(wg_ctx *ctx, uint32_t nsplit, uint64_t workspace_bytes, uint32_t outputs, uint32_t y_extent, float *out, uint32_t out_ld, uint64_t out_batch,
+                      wgk_q_dst *d);
+// ... the one combine pass: out = the partials added in a fixed order. Launch only; the caller logs its family's tag. index64: the kernel's instance that indexes
+// an output with 64 bits (the Gemm families) or with 32 (the Gemv families)
+int wgk_q_combine(wg_ctx *ctx, bool index64, const float *part, uint32_t nsplit, uint32_t outputs, uint32_t y_extent, uint32_t mats, float *out, uint32_t ld_out,
+                  uint64_t out_batch);
+// r / G as the element-by-element kernels compute it: r >> shift (G a power of two); 32: one group (G >= extent); 255: divide
+inline uint32_t wgk_q_group_shift(uint32_t group_rows, uint32_t extent) {
+    return group_rows >= extent ? 32u : (group_rows & (group_rows - 1u)) == 0u ? (uint32_t)__builtin_ctz(group_rows) : 255u;
+}
+// the groups as the MFMA kernels of wg_gemm_q8 / wg_gemm_q4 count them
+struct wgk_q_groups {
+    uint32_t g_eff;            // the rows of a group as the step counter sees them (G, or 2^32 - step for one group per output)
+    uint32_t groups_per_split; // k_per_split / G where G < k (a split begins at a group's first row), else 0
+    uint32_t g_shift;          // wgk_q_group_shift(G, k)
+};
+inline wgk_q_groups wgk_q_group_args(uint32_t group_rows, uint32_t k, uint32_t k_per_split, uint32_t step) {
+    const bool one_group = group_rows >= k;
+    return { one_group ? 0u - step : group_rows, one_group ? 0u : k_per_split / group_rows, wgk_q_group_shift(group_rows, k) };
+}
 // wg_quantize_q8 (quantize_q8.hip): q / scales from src (src_dtype elements). quantize_q8_plan is the launcher's choice, a pure function; the launcher logs its tag.
 wg_quantize_q8_plan quantize_q8_plan(const wg_quantize_q8_query &q);
 int wgk_quantize_q8(wg_ctx *ctx, const wg_quantize_q8_plan &p, wg_dtype src_dtype, uint32_t group_rows, uint32_t rows, uint32_t cols, uint32_t nmats, int8_t *q, uint32_t q_ld,
